@@ -11,8 +11,13 @@ One "step" = one pass of the hot path over one batch per GPU: x_T -> 50 x (UNetM
 when N > 1).  Workload = BASELINE.json configs[1]: bs=8/GPU, 256x256 px (latent 4x32x32),
 50-step DDIM, eta=0, 1 UNet forward per step (no CFG), text-only conditioning [8,87,768],
 fp16 kernels with fp32 accumulation, synthetic inputs and recipe weights already resident
-in HBM.  value = images/s over all ranks.  The config-true 256x192 (latent 32x24) rate is
-reported next to it.
+in HBM.  value = images/s over all ranks.
+
+A plain run sets up, warms up, times the K steps and prints the result line, nothing else.
+--full adds every secondary figure: the serial (one batch at a time) rate, the config-true
+256x192 (latent 32x24) rate, the per-class / per-kernel roofline replays, the VAE decode time
+and the CPU baseline.  --dump-outputs DIR writes the images of the last timed step as
+DIR/images.npy (float32), for comparing two builds output for output.
 """
 import argparse
 import contextlib
@@ -121,6 +126,25 @@ def gathered(step_fn):
     images (RCCL over xGMI; enqueued on the stream the decode ran on, inside the timed region)."""
     from upgpt_amd import dist as D
     return lambda: D.all_gather_images(step_fn())
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """{name: tensor} -> out_dir/<name>.npy in float32.  An array larger than DUMP_LIMIT_BYTES (split evenly between the
+    arrays) is written as a fixed, seeded sample of its flattened elements: the same elements on every run of the same
+    shape, so two builds compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    per_array = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > per_array:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, per_array // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        log("[bench] wrote %s (%s float32)" % (os.path.join(out_dir, name + ".npy"), "x".join(map(str, a.shape))))
 
 
 def kernel_class_profile(model, wl, reps=20):
@@ -628,9 +652,15 @@ def main():
     ap.add_argument("--latent", default="32x32", help="HxW of the latent (32x32 = 256x256 px)")
     ap.add_argument("--lanes", type=int, default=int(os.environ.get("UPGPT_BENCH_LANES", "4")),
                     help="independent bs=8 batches in flight per GPU (execution lanes, upgpt_amd/lanes.py); 1 = one batch "
-                         "at a time (the serial loop, also reported as `serial` when lanes > 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+                         "at a time (the serial loop, also reported as `serial` by --full when lanes > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: serial rate, config-true 256x192 rate, "
+                         "batch-16 control, roofline / per-class replays, VAE decode, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the images of the last timed step to DIR/images.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="(with --full) skip the config-true 256x192 rate and the batch-16 control")
     ap.add_argument("--cfg", type=float, default=0.0,
                     help="also time the main workload with classifier-free guidance at this scale (UNet on 2*B rows)")
     ap.add_argument("--encoders", action="store_true",
@@ -667,7 +697,7 @@ def main():
     wls = [Workload(model, args.batch, hw, args.ddim_steps, seed=D.rank_seed(1000 * l, rank)) for l in range(n_lanes)]
     wl = wls[0]
     serial = None
-    if n_lanes > 1:
+    if n_lanes > 1 and args.full:
         # the same steps one batch at a time (what `value` was through round 4): lane 0 alone, same barriers, measured
         # BEFORE the lane pool exists, i.e. with the launch choices tuned for one forward having the chip to itself
         ks = max(2, min(args.steps, 6))
@@ -690,6 +720,9 @@ def main():
     lane_ms = pool.lane_step_ms() if n_lanes > 1 else None
     dt = D.max_over_ranks(dt, dev)
     assert out.shape[0] == args.batch * world and torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:
+        # copied to the host before anything else runs on the device (the images may live in a plan's own buffer)
+        dump_outputs(args.dump_outputs, {"images": out})
     images = args.batch * world * args.steps
     result = {
         "metric": "256x256 images/sec, 50-step DDIM, bs=8/GPU; UNet MFMA util %",
@@ -709,12 +742,15 @@ def main():
     }
     if serial is not None:
         result["serial"] = serial
+    if lane_ms is not None:
         # a batch's own time in flight (device time between the ends of consecutive steps of a lane), per lane
         result["step_latency_ms"] = [round(sum(v) / max(1, len(v)), 2) for v in lane_ms]
     if rank == 0:
         a = arch.UNetArch(**synth.BBOX_UNET)
         flops_fwd = a.flops(args.batch, hw[0], hw[1], 87)
         result["mfma_util_whole_job"] = flops_fwd * args.ddim_steps * args.steps / dt / (PEAK_MFMA_F16_TFLOPS * 1e12)
+    # ---- --full: every figure beyond the headline line (each takes device runs of its own)
+    if rank == 0 and args.full:
         lanes_prof = lanes_class_profile(model, pool, wl) if n_lanes > 1 else None
         cfg_true_lanes = None
         if n_lanes > 1 and not args.no_secondary and world == 1 and hw != (32, 24):
@@ -846,7 +882,10 @@ def main():
                     "unet_fwd_ms_graph": unet_forward_ms(model, wl2),
                     "algorithmic_gflop_per_fwd": a.flops(args.batch, 32, 24, 87) / 1e9}
             result["config_true_256x192"] = ser2 if cfg_true_lanes is None else dict(cfg_true_lanes, serial=ser2)
-        # the other BASELINE configurations, in the bench's own mode (lanes > 1: that many batches in flight)
+    if rank == 0:
+        # the other BASELINE configurations, each on request (--cfg / --encoders / --upscale), in the bench's own mode
+        # (lanes > 1: that many batches in flight)
+        from upgpt_amd import _lib as _L
         sec_pool = pool if n_lanes > 1 else None
         _L.set_concurrency(n_lanes)
         if args.cfg and world == 1:
@@ -877,7 +916,7 @@ def main():
             # channels 3): BASELINE configs[4] config-true, 3869.7 GF per forward
             result["config_upscale_config_true"] = dict(upscale_secondary(args.ddim_steps, dev, hw=(128, 96), pool=sec_pool),
                                                         latent="3x128x96", batch=4)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             result["cpu_baseline"] = cpu_baseline(hw, args.ddim_steps, args.batch)
         print(json.dumps(result), flush=True)
     D.barrier()

@@ -38,11 +38,27 @@ def test_state_dict_layout_matches_reference_manifest(kind):
     assert not missing and not unexpected
 
 
-def test_reference_yaml_parses_unchanged():
-    p = "/root/reference/configs/deepfashion/bbox.yaml"
-    if not os.path.exists(p):
-        pytest.skip("reference tree not present on this box")
-    cfg = load_config(p)["model"]
+def test_reference_yaml_parses_unchanged(tmp_path):
+    """A full training config in the reference's layout (configs/deepfashion/bbox.yaml: the CLIP text / image encoders as
+    conditioning stages, a first-stage checkpoint path, the lr scheduler and the data / lightning blocks this package never
+    reads) loads through load_config + instantiate_from_config as it stands.  Built from the model block of
+    configs/upgpt_bbox_model.yaml, which restates the reference's values."""
+    import yaml
+    full = load_config(os.path.join(ROOT, "configs", "upgpt_bbox_model.yaml"))
+    params = full["model"]["params"]
+    params["first_stage_config"]["params"]["ckpt_path"] = "models/first_stage_models/kl-f8-deepfashion/deepfashion_256_v2.ckpt"
+    params["cond_stage_config"] = {"target": "ldm.modules.encoders.modules.FrozenCLIPEmbedder"}
+    params["extra_cond_stages"]["style_cond"]["target"] = "ldm.modules.encoders.modules.FrozenClipImageEmbedder2"
+    params["scheduler_config"] = {"target": "ldm.lr_scheduler.LambdaLinearScheduler",
+                                  "params": {"warm_up_steps": [1], "cycle_lengths": [10 ** 13], "f_start": [1e-6],
+                                             "f_max": [1.0], "f_min": [1.0]}}
+    full["data"] = {"target": "main.DataModuleFromConfig", "params": {"batch_size": 12, "num_workers": 12, "train": {
+        "target": "ldm.data.deepfashion_inshop.DeepFashionPair", "params": {"input_mask_type": "bbox", "image_size": [256, 192]}}}}
+    full["lightning"] = {"trainer": {"benchmark": True, "max_epochs": 100},
+                         "callbacks": {"image_logger": {"target": "main.ImageLogger", "params": {"batch_frequency": 1000}}}}
+    p = tmp_path / "bbox.yaml"
+    p.write_text(yaml.safe_dump(full, sort_keys=False))
+    cfg = load_config(str(p))["model"]
     cfg["params"]["first_stage_config"]["params"]["ckpt_path"] = None
     m = instantiate_from_config(cfg)
     assert type(m).__name__ == "LatentDiffusion" and m.model.conditioning_key == "hybrid"
