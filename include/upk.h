@@ -485,6 +485,22 @@ int upk_ddim_step_f32(upk_ctx* ctx, float* x, const float* eps, const float* coe
 int upk_ddim_step_cfg_f32(upk_ctx* ctx, float* x, const float* eps2, const float* coefs,
                           const float* noise, const int32_t* step, float* pred_x0, void* xin,
                           int ld_xin, int batch, int c, int hw, float scale, upk_stream stream);
+/* One DDPM ancestral step (ddpm.py:1125-1187; with a mask also the q_sample blend of ddpm.py:1282-1283), fp32 NCHW,
+ * n = B*C*H*W elements; row = coefs + 8 * (*step):
+ *   {sqrt(1/a_t), sqrt(1/a_t - 1), posterior_mean_coef1, posterior_mean_coef2,
+ *    nonzero(t) * exp(0.5 * posterior_log_variance_clipped), sqrt(a_t), sqrt(1 - a_t), 0}
+ *   x_recon = UPK_DDPM_X0 ? model_out : row[0]*x - row[1]*model_out; clamped to [-1, 1] with UPK_DDPM_CLIP
+ *   x_prev = row[2]*x_recon + row[3]*x + row[4]*noise
+ *   mask != NULL: x_prev = mask*(row[5]*x0 + row[6]*noise2) + (1 - mask)*x_prev   (the SAME t as the step)
+ * noise / noise2: [n_steps, n] standard normals (temperature folded in by the caller) indexed by *step, may be NULL;
+ * x0, mask: [n] (mask expanded to the latent's shape), may be NULL; pred_x0 (may be NULL) <- x_recon.  Refreshes
+ * the UNet stem input xin like upk_ddim_step_f32.  x is updated in place. */
+#define UPK_DDPM_X0 0x1
+#define UPK_DDPM_CLIP 0x2
+int upk_ddpm_step_f32(upk_ctx* ctx, float* x, const float* model_out, const float* coefs,
+                      const float* noise, const float* noise2, const float* x0, const float* mask,
+                      const int32_t* step, float* pred_x0, void* xin, int ld_xin, int batch, int c, int hw,
+                      int flags, upk_stream stream);
 /* One model evaluation of the PLMS sampler (ldm/models/diffusion/plms.py:177-236; eta = 0), *step = evaluation
  * counter k (S + 1 evaluations for S steps: the first step evaluates twice, pseudo improved Euler):
  *   k = 0: predictor x~ = ddim(x, e0, coef[0]) goes to xin only; k = 1: e' = (e0 + eps)/2, x <- ddim(x, e', coef[0]);
@@ -496,7 +512,7 @@ int upk_plms_step_f32(upk_ctx* ctx, float* x, const float* eps, const float* coe
                       float* hist, float* pred_x0, void* xin, int ld_xin, int batch, int c, int hw,
                       float cfg_scale, int cfg, upk_stream stream);
 /* With done != NULL the sampler step kernels launched afterwards (upk_ddim_step_f32, upk_ddim_step_cfg_f32,
- * upk_plms_step_f32) add 1 to *step THEMSELVES once every workgroup has read it (done: a zero-initialised device
+ * upk_plms_step_f32, upk_ddpm_step_f32) add 1 to *step THEMSELVES once every workgroup has read it (done: a zero-initialised device
  * int32 they use as arrival counter and leave at zero) — one launch less per sampler step than upk_advance_step.
  * done == NULL restores the plain behaviour.  Host-side state of the context: set it around the calls. */
 int upk_step_autoadvance(upk_ctx* ctx, int32_t* done);

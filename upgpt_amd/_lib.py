@@ -25,7 +25,7 @@ SYMBOLS = [
     "upk_attention_f16", "upk_groupnorm_nhwc_f16", "upk_groupnorm_stats_nhwc_f16", "upk_groupnorm_chunks", "upk_groupnorm_apply_nhwc_f16", "upk_groupnorm_finalize_f32", "upk_groupnorm_ws_bytes",
     "upk_layernorm_f16", "upk_timestep_embed_f16",
     "upk_nchw_f32_to_nhwc_f16", "upk_nhwc_f16_to_nchw_f32", "upk_f32_to_f16", "upk_ddim_step_f32",
-    "upk_ddim_step_cfg_f32", "upk_plms_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
+    "upk_ddim_step_cfg_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
     "upk_patchify_nchw_f32_f16", "upk_vit_assemble_f16", "upk_gather_rows_f16",
     "upk_advance_step", "upk_step_autoadvance", "upk_kernel_launches", "upk_graph_begin", "upk_graph_end", "upk_graph_launch", "upk_graph_destroy",
     "upk_prof_enable", "upk_prof_collect",
@@ -33,6 +33,7 @@ SYMBOLS = [
 ]
 
 F_SILU, F_GEGLU, F_OUT_F32, F_OUT_NCHW_F32, F_UPSAMPLE2X, F_PAD_ASYM = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
+DDPM_X0, DDPM_CLIP = 0x1, 0x2  # upk_ddpm_step_f32 flags
 F_QUICKGELU = 0x40
 NUM_CLASSES = 5
 CLASS_NAMES = ["igemm", "attention", "groupnorm", "layernorm", "other"]
@@ -175,6 +176,7 @@ def load_library(path=None):
             "upk_ddim_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
             "upk_ddim_step_cfg_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]),
             "upk_plms_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),
+            "upk_ddpm_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
             "upk_advance_step": (C.c_int, [vp, vp, vp]),
             "upk_step_autoadvance": (C.c_int, [vp, vp]),
             "upk_kernel_launches": (C.c_longlong, [vp, i32]),
@@ -322,6 +324,11 @@ class Context:
     def ddim_step_cfg(self, x, eps2, coefs, noise, step, pred_x0, xin, ld_xin, batch, c, hw, scale):
         self._chk(self.lib.upk_ddim_step_cfg_f32(self.h, _ptr(x), _ptr(eps2), _ptr(coefs), _ptr(noise), _ptr(step),
                                                  _ptr(pred_x0), _ptr(xin), ld_xin, batch, c, hw, float(scale), self._s()))
+
+    def ddpm_step(self, x, model_out, coefs, noise, noise2, x0, mask, step, pred_x0, xin, ld_xin, batch, c, hw, flags):
+        self._chk(self.lib.upk_ddpm_step_f32(self.h, _ptr(x), _ptr(model_out), _ptr(coefs), _ptr(noise), _ptr(noise2),
+                                             _ptr(x0), _ptr(mask), _ptr(step), _ptr(pred_x0), _ptr(xin), ld_xin, batch,
+                                             c, hw, int(flags), self._s()))
 
     def advance_step(self, step):
         self._chk(self.lib.upk_advance_step(self.h, _ptr(step), self._s()))

@@ -217,6 +217,39 @@ __global__ void ddim_step_kernel(float* x, const float* eps, const float* coefs,
   if (step) step_advance(step, done);
 }
 
+// One DDPM posterior step, ddpm.py:1125-1187 (+ the q_sample blend of 1282-1283), in one launch (see include/upk.h
+// for the coefficient table and the flags).
+__global__ void ddpm_step_kernel(float* x, const float* mo, const float* coefs, const float* noise, const float* noise2,
+                                 const float* x0, const float* mask, const int* step, float* pred_x0, f16* xin,
+                                 int ld_xin, int c, int hw, long n, int flags, int* done) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int st = step ? *step : 0;
+  if (idx < n) {
+    const float* cf = coefs + 8 * st;
+    const float xv = x[idx], m = mo[idx];
+    float xr = (flags & UPK_DDPM_X0) ? m : cf[0] * xv - cf[1] * m;
+    if (flags & UPK_DDPM_CLIP) xr = fminf(fmaxf(xr, -1.f), 1.f);
+    float xp = cf[2] * xr + cf[3] * xv;
+    if (noise) xp += cf[4] * noise[(long)st * n + idx];
+    if (mask) {
+      float q = cf[5] * x0[idx];
+      if (noise2) q += cf[6] * noise2[(long)st * n + idx];
+      const float mk = mask[idx];
+      xp = mk * q + (1.f - mk) * xp;
+    }
+    x[idx] = xp;
+    if (pred_x0) pred_x0[idx] = xr;
+    if (xin) {
+      const long p = idx % hw;
+      const long t = idx / hw;
+      const long ch = t % c;
+      const long b = t / c;
+      xin[(b * hw + p) * ld_xin + ch] = (f16)xp;
+    }
+  }
+  if (step) step_advance(step, done);
+}
+
 // Classifier-free guidance inside the update (ddim.py:173-178): the UNet ran on [uncond ; cond] (2*batch rows),
 // eps = e_u + scale * (e_c - e_u); the new latent refreshes BOTH halves of the UNet stem input.
 __global__ void ddim_step_cfg_kernel(float* x, const float* eps2, const float* coefs, const float* noise, const int* step,
@@ -429,6 +462,23 @@ extern "C" int upk_ddim_step_f32(upk_ctx* ctx, float* x, const float* eps, const
   hipLaunchKernelGGL(ddim_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, x, eps,
                      coefs, noise, step, pred_x0, (f16*)xin, ld_xin, c, hw, n, ctx->step_done);
   return upk_check_launch(ctx, "ddim_step");
+}
+
+extern "C" int upk_ddpm_step_f32(upk_ctx* ctx, float* x, const float* model_out, const float* coefs, const float* noise,
+                                 const float* noise2, const float* x0, const float* mask, const int32_t* step,
+                                 float* pred_x0, void* xin, int ld_xin, int batch, int c, int hw, int flags,
+                                 upk_stream stream_) {
+  if (!ctx) return UPK_EINVAL;
+  if (!x || !model_out || !coefs || batch <= 0 || c <= 0 || hw <= 0) return upk_fail(ctx, UPK_EINVAL, "ddpm_step: bad args");
+  if (mask && !x0) return upk_fail(ctx, UPK_EINVAL, "ddpm_step: mask without x0");
+  if (flags & ~(UPK_DDPM_X0 | UPK_DDPM_CLIP)) return upk_fail(ctx, UPK_EINVAL, "ddpm_step: unknown flags");
+  if (xin && ld_xin < c) return upk_fail(ctx, UPK_EINVAL, "ddpm_step: ld_xin < c");
+  const long n = (long)batch * c * hw;
+  upk_prof_scope prof(ctx, UPK_CLS_OTHER, (hipStream_t)stream_);
+  hipLaunchKernelGGL(ddpm_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, x,
+                     model_out, coefs, noise, noise2, x0, mask, step, pred_x0, (f16*)xin, ld_xin, c, hw, n, flags,
+                     ctx->step_done);
+  return upk_check_launch(ctx, "ddpm_step");
 }
 
 extern "C" int upk_ddim_step_cfg_f32(upk_ctx* ctx, float* x, const float* eps2, const float* coefs, const float* noise,

@@ -151,16 +151,8 @@ class DDIMSampler(object):
             with (host_io() if (fresh or on_host or with_noise) else contextlib.nullcontext()):
                 img = torch.randn(shape, device=dev) if x_T is None else x_T.to(dev, torch.float32)
                 st.x.copy_(img)
-                plan.load_x_nchw(torch.cat([st.x, st.x]) if cfg else st.x, 0, 0)
-                ncat = 0
-                if c_concat is not None:
-                    ncat = c_concat.shape[1]
-                    plan.load_x_nchw(c_concat, C, plan.cin_pad)
-                require(C + ncat == unet.in_channels, lambda: "latent %d + concat %d != UNet in_channels %d" % ( C, ncat, unet.in_channels), ValueError)
-                plan.load_context(c_cross)
-                if fresh_rows:
-                    plan.t_rows.copy_(torch.as_tensor(np.asarray(timesteps)[order].astype(np.float32)))
-                    plan._t_rows_key = rkey
+                plan.load_sampler_inputs(torch.cat([st.x, st.x]) if cfg else st.x, c_concat, c_cross, unet.in_channels,
+                                         rkey, np.asarray(timesteps)[order].astype(np.float32))
                 if fresh_coefs:
                     st.coefs.copy_(ddim_coefficient_table(self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sigmas,
                                                           self.ddim_sqrt_one_minus_alphas, order))

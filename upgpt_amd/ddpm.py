@@ -20,10 +20,13 @@ import numpy as np
 import torch
 from torch import nn
 
+from .ancestral import AncestralSampling
 from .config import count_params, instantiate_from_config, to_plain
 from .ddim import DDIMSampler
 from .ema import LitEma
+from .grid import make_grid
 from .schedule import extract_into_tensor, make_beta_schedule
+from .vae import AutoencoderKL
 from ._check import require
 
 
@@ -204,8 +207,8 @@ class DDPM(nn.Module):
     p_losses = configure_optimizers = validation_step = training_step
 
 
-class LatentDiffusion(DDPM):
-    """ddpm.py:433-1547, inference surface."""
+class LatentDiffusion(AncestralSampling, DDPM):
+    """ddpm.py:433-1547, inference surface; the DDPM ancestral sampler comes from AncestralSampling."""
 
     def __init__(self, first_stage_config, cond_stage_config, num_timesteps_cond=None, cond_stage_key="image",
                  cond_stage_trainable=False, concat_mode=True, cond_stage_forward=None, conditioning_key=None,
@@ -403,33 +406,76 @@ class LatentDiffusion(DDPM):
     def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
         """ddpm.py:1312-1325."""
         if not ddim:
-            raise NotImplementedError("DDPM ancestral sampling (ddim=False) is not used by the UPGPT callers")
+            return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, **kwargs)
         shape = (self.channels, *self.image_size)
         return DDIMSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
+
+    def _get_denoise_row_from_list(self, samples, desc="", force_no_decoder_quantization=False):
+        """ddpm.py:557-567: decode the logged latents, one grid row per sample.  `samples` is DDIM's intermediates dict
+        or the list the DDPM loops return (the reference indexes both with 'x_inter' and fails on the list)."""
+        zs = samples["x_inter"] if isinstance(samples, dict) else samples
+        row = torch.stack([self.decode_first_stage(z.to(self.device)) for z in zs])  # n_log_step, n_row, C, H, W
+        return make_grid(row.transpose(0, 1).flatten(0, 1), nrow=row.shape[0])
 
     @torch.no_grad()
     def log_images(self, batch, N=8, n_row=4, sample=True, ddim_steps=200, ddim_eta=1., return_keys=None,
                    quantize_denoised=False, inpaint=False, plot_denoise_rows=False, plot_progressive_rows=False,
                    plot_diffusion_rows=False, seed=None, **kwargs):
-        """ddpm.py:1380-1499 — the path InferenceModel.generate drives (generate_utils.py:159-169):
-        conditioning assembly -> EMA scope -> DDIM -> decode.  Returns {'reconstruction'?, 'samples'}."""
-        if inpaint or plot_denoise_rows or plot_progressive_rows or plot_diffusion_rows or quantize_denoised:
-            raise NotImplementedError("only the sampling branch of log_images is implemented")
-        if ddim_steps is None:
-            raise NotImplementedError("ddim_steps=None (DDPM sampler)")
-        _, cond, x, xrec, _ = self.get_input(batch, self.first_stage_key, return_first_stage_outputs=True,
+        """ddpm.py:1380-1499 — the path InferenceModel.generate drives (generate_utils.py:159-169): conditioning
+        assembly -> EMA scope -> DDIM (ddim_steps=None: the DDPM chain) -> decode, and the reference's plotting rows.
+        Returns {'reconstruction'?, 'samples', ...}."""
+        use_ddim = ddim_steps is not None
+        z, cond, x, xrec, _ = self.get_input(batch, self.first_stage_key, return_first_stage_outputs=True,
                                              force_c_encode=True, return_original_cond=True, bs=N)
         n = min(x.shape[0], N)
+        n_row = min(x.shape[0], n_row)
         log = {} if xrec is None else {"reconstruction": xrec}
+        require(z is not None or not (plot_diffusion_rows or inpaint),
+                "diffusion rows and inpainting need the first stage's encoder", NotImplementedError)
+        if plot_diffusion_rows:  # q_sample of the encoded batch along the schedule (ddpm.py:1405-1420)
+            z_start = z[:n_row]
+            rows = []
+            for t in range(self.num_timesteps):
+                if t % self.log_every_t == 0 or t == self.num_timesteps - 1:
+                    tt = torch.full((n_row,), t, device=self.device, dtype=torch.long)
+                    rows.append(self.decode_first_stage(self.q_sample(z_start, tt, noise=torch.randn_like(z_start))))
+            rows = torch.stack(rows)  # n_log_step, n_row, C, H, W
+            log["diffusion_row"] = make_grid(rows.transpose(0, 1).flatten(0, 1), nrow=rows.shape[0])
         if sample:
             x_T = None
             if seed:  # one seeded latent shared by the batch (ddpm.py:1422-1426)
                 torch.manual_seed(seed)
                 x_T = torch.randn((1, self.channels, *self.image_size), device=self.device).repeat(n, 1, 1, 1)
             with self.ema_scope("Plotting"):
-                z, _ = self.sample_log(cond=cond, batch_size=n, ddim=True, ddim_steps=ddim_steps, eta=ddim_eta,
-                                       x_T=x_T, **kwargs)
-            log["samples"] = self.decode_first_stage(z)
+                samples, z_denoise_row = self.sample_log(cond=cond, batch_size=n, ddim=use_ddim, ddim_steps=ddim_steps,
+                                                         eta=ddim_eta, x_T=x_T, **kwargs)
+            log["samples"] = self.decode_first_stage(samples)
+            if plot_denoise_rows:
+                log["denoise_row"] = self._get_denoise_row_from_list(z_denoise_row)
+            # an AutoencoderKL first stage has nothing to quantize: the reference skips the branch (ddpm.py:1452-1454)
+            require(not quantize_denoised or isinstance(self.first_stage_model, AutoencoderKL),
+                    "quantize_denoised needs a VQ first stage (not on the UPGPT path)", NotImplementedError)
+            if inpaint:  # a centre square is filled in (mask 0), the rest is kept (ddpm.py:1463-1484)
+                h, w = z.shape[2], z.shape[3]
+                mask = torch.ones(n, h, w, device=self.device)
+                mask[:, h // 4:3 * h // 4, w // 4:3 * w // 4] = 0.
+                mask = mask[:, None, ...]
+                with self.ema_scope("Plotting Inpaint"):
+                    samples, _ = self.sample_log(cond=cond, batch_size=n, ddim=use_ddim, eta=ddim_eta,
+                                                 ddim_steps=ddim_steps, x0=z[:n], mask=mask)
+                log["samples_inpainting"] = self.decode_first_stage(samples.to(self.device))
+                log["mask"] = mask
+                # "outpainting" runs with the SAME mask as the inpainting, as the reference does: a second draw of
+                # the same task (its own x_T), not the complementary one
+                with self.ema_scope("Plotting Outpaint"):
+                    samples, _ = self.sample_log(cond=cond, batch_size=n, ddim=use_ddim, eta=ddim_eta,
+                                                 ddim_steps=ddim_steps, x0=z[:n], mask=mask)
+                log["samples_outpainting"] = self.decode_first_stage(samples.to(self.device))
+        if plot_progressive_rows:
+            with self.ema_scope("Plotting Progressives"):
+                _, progressives = self.progressive_denoising(cond, shape=(self.channels, *self.image_size),
+                                                             batch_size=n)
+            log["progressive_row"] = self._get_denoise_row_from_list(progressives, desc="Progressive Generation")
         if return_keys and any(k in log for k in return_keys):
             return {k: log[k] for k in return_keys}
         return log

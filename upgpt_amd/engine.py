@@ -225,10 +225,27 @@ class UNetPlan(Emitter):
     # ---- host-facing helpers
     def close(self):
         """Releases the graphs of the sampler states attached to this plan (ddim.py / plms.py fast paths)."""
-        for attr in ("_sampler_state", "_sampler_state_cfg", "_plms_state", "_plms_state_cfg"):
+        for attr in ("_sampler_state", "_sampler_state_cfg", "_plms_state", "_plms_state_cfg", "_ddpm_state"):
             st = self.__dict__.pop(attr, None)
             if st is not None:
                 st.close()
+
+    def load_sampler_inputs(self, x, c_concat, c_cross, in_channels, rows_key, t_rows):
+        """The per-call uploads of a sampler fast path: the latent (channels [0, C) of the stem input), the concat
+        conditioning behind it, the context, and the timestep rows when `rows_key` differs from what the plan holds
+        (one buffer shared by every sampler state of the plan)."""
+        C = x.shape[1]
+        self.load_x_nchw(x, 0, 0)
+        ncat = 0
+        if c_concat is not None:
+            ncat = c_concat.shape[1]
+            self.load_x_nchw(c_concat, C, self.cin_pad)
+        require(C + ncat == in_channels, lambda: "latent %d + concat %d != UNet in_channels %d" % (C, ncat, in_channels),
+                ValueError)
+        self.load_context(c_cross)
+        if getattr(self, "_t_rows_key", None) != rows_key:
+            self.t_rows.copy_(torch.as_tensor(t_rows))
+            self._t_rows_key = rows_key
 
     def load_context(self, context):
         """context: [B, n_ctx, context_dim] tensor (any float dtype / device)."""
@@ -366,21 +383,28 @@ class SamplerState:
     pred_x0, the per-step coefficient / noise tables and the captured step graph
     (UNet body -> upk_ddim_step_f32 -> upk_advance_step)."""
 
-    def __init__(self, plan: UNetPlan, channels, cfg=False, plms=False):
+    def __init__(self, plan: UNetPlan, channels, cfg=False, plms=False, ddpm=False):
         """cfg: classifier-free guidance — the plan runs 2*B rows ([unconditional ; conditional], ddim.py:173-178),
         the latent state has B = plan.B // 2 samples and the update combines the two halves of eps.
-        plms: the graph is one PLMS model evaluation (upk_plms_step_f32; plan rows = evaluations = steps + 1)."""
+        plms: the graph is one PLMS model evaluation (upk_plms_step_f32; plan rows = evaluations = steps + 1).
+        ddpm: the graph is one DDPM ancestral step (upk_ddpm_step_f32; plan rows = timesteps of the chain, coefficient
+        rows of 8).  Its posterior noise table [rows, n] is always there, and a masked chain adds the q_sample noise
+        table, x0 and the expanded mask: at B = 8, 32x24 and 1000 steps each table is 1000 * 24576 * 4 B = 98 MB."""
         require(plan.mode == "sampler", "SamplerState needs a sampler-mode plan", ValueError)
         self.plan = plan
         self.cfg = bool(cfg)
         self.plms = bool(plms)
         require(not cfg or plan.B % 2 == 0, "guidance runs [uncond ; cond]: the plan's batch must be even", ValueError)
+        require(not (ddpm and (cfg or plms)), "the DDPM step has no guidance and no PLMS history", ValueError)
+        self.ddpm = bool(ddpm)
+        self.ddpm_flags, self.masked = 0, False  # (the DDPM variant the next graph() / step_eager() runs)
+        self.noise2 = self.x0 = self.mask = None
         B, H, W, R = (plan.B // 2 if cfg else plan.B), plan.H, plan.W, plan.rows
         self.B = B
         self.C = channels
         self.x = plan.alloc(B, channels, H, W, dtype=torch.float32)
         self.pred_x0 = plan.alloc(B, channels, H, W, dtype=torch.float32)
-        self.coefs = plan.alloc(R, 4, dtype=torch.float32)
+        self.coefs = plan.alloc(R, 8 if ddpm else 4, dtype=torch.float32)
         self.noise = None
         self.graphs = {}
         self.step_done = plan.alloc(1, dtype=torch.int32, zero=True)  # arrival counter of the step kernels
@@ -402,6 +426,15 @@ class SamplerState:
             self.noise = p.alloc(p.rows, self.B * self.C * p.H * p.W, dtype=torch.float32)
         return self.noise
 
+    def ensure_mask(self):
+        """The masked-chain buffers (DDPM): q_sample noise table, x0 and the mask, both expanded to the latent."""
+        if self.mask is None:
+            p, n = self.plan, self.B * self.C * self.plan.H * self.plan.W
+            self.noise2 = p.alloc(p.rows, n, dtype=torch.float32)
+            self.x0 = p.alloc(n, dtype=torch.float32)
+            self.mask = p.alloc(n, dtype=torch.float32)
+        return self.noise2, self.x0, self.mask
+
     def _emit_tail(self, stream, with_noise, scale=1.0):
         p = self.plan
         nz = self.noise.data_ptr() if with_noise else None
@@ -414,7 +447,14 @@ class SamplerState:
 
     def _emit_step(self, stream, nz, scale):
         p = self.plan
-        if self.plms:
+        if self.ddpm:
+            m = self.masked
+            ptr = lambda t: t.data_ptr() if m else None
+            p.ctx._chk(p.lib.upk_ddpm_step_f32(p.hctx, self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(), nz,
+                                               ptr(self.noise2), ptr(self.x0), ptr(self.mask), p.step.data_ptr(),
+                                               self.pred_x0.data_ptr(), p.xin.t.data_ptr(), p.xin.ld, self.B, self.C,
+                                               p.H * p.W, int(self.ddpm_flags), stream))
+        elif self.plms:
             require(nz is None, "PLMS runs with eta = 0", ValueError)
             p.ctx._chk(p.lib.upk_plms_step_f32(p.hctx, self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(),
                                                p.step.data_ptr(), self.hist.data_ptr(), self.pred_x0.data_ptr(),
@@ -439,6 +479,8 @@ class SamplerState:
         graph serves every position of the loop; the guidance scale is a kernel argument, so each scale value gets its
         own graph).  nsteps > 1 saves the graph-to-graph launch gap of the steps inside."""
         key = (with_noise, float(scale) if self.cfg else 1.0) + ((int(nsteps),) if nsteps != 1 else ())
+        if self.ddpm:
+            key += ("ddpm", int(self.ddpm_flags), bool(self.masked))
         g = self.graphs.pop(key, None)
         if g is not None:
             self.graphs[key] = g  # (most recently used last: eviction takes the least recently used graph)
@@ -446,6 +488,8 @@ class SamplerState:
             p = self.plan
             if with_noise:
                 self.ensure_noise()
+            if self.masked:
+                self.ensure_mask()
             with L.host_io():  # (no other lane uploads from the host while this thread captures)
                 side = torch.cuda.Stream(device=p.dev)
                 side.wait_stream(torch.cuda.current_stream(p.dev))

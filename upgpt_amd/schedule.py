@@ -4,7 +4,8 @@ Numerics follow the reference exactly because the tables are tiny and precision-
 betas / alphas_cumprod in float64 numpy then stored fp32 (util.py:21-43, ddpm.py:125-146);
 DDIM selection and sigmas per util.py:46-74.  The per-step scalars that the reference
 re-materialises with torch.full every step (ddim.py:189-192) are folded here into ONE
-device table of 4 fp32 coefficients per step for upk_ddim_step_f32.
+device table of 4 fp32 coefficients per step for upk_ddim_step_f32 (8 per step for the DDPM
+step, upk_ddpm_step_f32).
 """
 import numpy as np
 import torch
@@ -57,6 +58,21 @@ def ddim_coefficient_table(alphas, alphas_prev, sigmas, sqrt_one_minus_alphas, o
     idx = torch.as_tensor(np.asarray(order), dtype=torch.long)
     a, ap, sg, sq = a[idx], ap[idx], sg[idx], sq[idx]
     return torch.stack([sq, 1.0 / a.sqrt(), ap.sqrt(), (1.0 - ap - sg ** 2).sqrt()], dim=1).contiguous()
+
+
+def ddpm_coefficient_table(model, t_order):
+    """[len(t_order), 8] fp32 rows of upk_ddpm_step_f32 for the DDPM timesteps `t_order` (loop order), gathered from
+    the model's fp32 schedule buffers and combined in fp32 as ddpm.py:1125-1187 does:
+    {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, posterior_mean_coef1, posterior_mean_coef2,
+     nonzero(t) * (0.5 * posterior_log_variance_clipped).exp(), sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, 0}.
+    The sampling temperature multiplies the noise (ddpm.py:1174), so it is folded into the noise table, not here."""
+    t = torch.as_tensor(np.asarray(t_order), dtype=torch.long)
+    buf = lambda name: getattr(model, name).detach().to("cpu", torch.float32)[t]
+    nonzero = 1 - (t == 0).float()
+    cols = [buf("sqrt_recip_alphas_cumprod"), buf("sqrt_recipm1_alphas_cumprod"), buf("posterior_mean_coef1"),
+            buf("posterior_mean_coef2"), nonzero * (0.5 * buf("posterior_log_variance_clipped")).exp(),
+            buf("sqrt_alphas_cumprod"), buf("sqrt_one_minus_alphas_cumprod"), torch.zeros(t.shape[0])]
+    return torch.stack(cols, dim=1).contiguous()
 
 
 def extract_into_tensor(a, t, x_shape):
