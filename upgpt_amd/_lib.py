@@ -330,6 +330,15 @@ class Context:
                                              _ptr(x0), _ptr(mask), _ptr(step), _ptr(pred_x0), _ptr(xin), ld_xin, batch,
                                              c, hw, int(flags), self._s()))
 
+    def plms_step(self, x, eps, coefs, step, hist, pred_x0, xin, ld_xin, batch, c, hw, cfg_scale=1.0, cfg=False):
+        self._chk(self.lib.upk_plms_step_f32(self.h, _ptr(x), _ptr(eps), _ptr(coefs), _ptr(step), _ptr(hist),
+                                             _ptr(pred_x0), _ptr(xin), ld_xin, batch, c, hw, float(cfg_scale), int(cfg),
+                                             self._s()))
+
+    def step_autoadvance(self, done):
+        """Arms (done: zeroed device int32) or disarms (None) the step kernels' own increment of *step."""
+        self._chk(self.lib.upk_step_autoadvance(self.h, _ptr(done)))
+
     def advance_step(self, step):
         self._chk(self.lib.upk_advance_step(self.h, _ptr(step), self._s()))
 
