@@ -485,6 +485,22 @@ int upk_ddim_step_f32(upk_ctx* ctx, float* x, const float* eps, const float* coe
 int upk_ddim_step_cfg_f32(upk_ctx* ctx, float* x, const float* eps2, const float* coefs,
                           const float* noise, const int32_t* step, float* pred_x0, void* xin,
                           int ld_xin, int batch, int c, int hw, float scale, upk_stream stream);
+/* The DDIM update for the editing calls: inpainting (sample(mask=, x0=), ddim.py:144-147) and chains that start inside
+ * the schedule (decode, ddim.py:222-241).  x / pred_x0 / noise / coefs / xin as for upk_ddim_step_f32, n = batch*C*HW;
+ * cfg != 0: eps holds [uncond ; cond] (2*batch rows), e = e_u + scale * (e_c - e_u), and BOTH halves of xin
+ * (2*batch*hw rows) are refreshed; cfg == 0: scale is ignored.
+ *   x_prev = the update of upk_ddim_step_f32 at row *step
+ *   mask != NULL and *step + 1 < n_rows:  x = mask * keep[*step + 1] + (1 - mask) * x_prev
+ *   otherwise:                            x = x_prev
+ * The reference blends BEFORE the model evaluation of a step; here that is the tail of the step before, so row r of
+ * keep ([n_rows, n] fp32) is q_sample(x0, t) of loop position r (row 0 is never read: the caller blends the first latent),
+ * and the last row's result is left unblended, as the reference returns it.  mask: [n], expanded to the latent's shape;
+ * mask == NULL (keep and n_rows are then ignored) is the plain update.  x_plain (may be NULL) <- the unblended x_prev,
+ * what the reference logs as x_inter; pred_x0, noise, xin, step may be NULL.  xin is refreshed from what went to x. */
+int upk_ddim_step_edit_f32(upk_ctx* ctx, float* x, const float* eps, const float* coefs, const float* noise,
+                           const float* keep, const float* mask, int n_rows, const int32_t* step, float* pred_x0,
+                           float* x_plain, void* xin, int ld_xin, int batch, int c, int hw, float scale, int cfg,
+                           upk_stream stream);
 /* One DDPM ancestral step (ddpm.py:1125-1187; with a mask also the q_sample blend of ddpm.py:1282-1283), fp32 NCHW,
  * n = B*C*H*W elements; row = coefs + 8 * (*step):
  *   {sqrt(1/a_t), sqrt(1/a_t - 1), posterior_mean_coef1, posterior_mean_coef2,
@@ -512,7 +528,7 @@ int upk_plms_step_f32(upk_ctx* ctx, float* x, const float* eps, const float* coe
                       float* hist, float* pred_x0, void* xin, int ld_xin, int batch, int c, int hw,
                       float cfg_scale, int cfg, upk_stream stream);
 /* With done != NULL the sampler step kernels launched afterwards (upk_ddim_step_f32, upk_ddim_step_cfg_f32,
- * upk_plms_step_f32, upk_ddpm_step_f32) add 1 to *step THEMSELVES once every workgroup has read it (done: a zero-initialised device
+ * upk_ddim_step_edit_f32, upk_plms_step_f32, upk_ddpm_step_f32) add 1 to *step THEMSELVES once every workgroup has read it (done: a zero-initialised device
  * int32 they use as arrival counter and leave at zero) — one launch less per sampler step than upk_advance_step.
  * done == NULL restores the plain behaviour.  Host-side state of the context: set it around the calls. */
 int upk_step_autoadvance(upk_ctx* ctx, int32_t* done);

@@ -25,7 +25,7 @@ SYMBOLS = [
     "upk_attention_f16", "upk_groupnorm_nhwc_f16", "upk_groupnorm_stats_nhwc_f16", "upk_groupnorm_chunks", "upk_groupnorm_apply_nhwc_f16", "upk_groupnorm_finalize_f32", "upk_groupnorm_ws_bytes",
     "upk_layernorm_f16", "upk_timestep_embed_f16",
     "upk_nchw_f32_to_nhwc_f16", "upk_nhwc_f16_to_nchw_f32", "upk_f32_to_f16", "upk_ddim_step_f32",
-    "upk_ddim_step_cfg_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
+    "upk_ddim_step_cfg_f32", "upk_ddim_step_edit_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
     "upk_patchify_nchw_f32_f16", "upk_vit_assemble_f16", "upk_gather_rows_f16",
     "upk_advance_step", "upk_step_autoadvance", "upk_kernel_launches", "upk_graph_begin", "upk_graph_end", "upk_graph_launch", "upk_graph_destroy",
     "upk_prof_enable", "upk_prof_collect",
@@ -175,6 +175,8 @@ def load_library(path=None):
             "upk_f32_to_f16": (C.c_int, [vp, vp, i32, i32, vp, i32, vp]),
             "upk_ddim_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
             "upk_ddim_step_cfg_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]),
+            "upk_ddim_step_edit_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, f32,
+                                                 i32, vp]),
             "upk_plms_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),
             "upk_ddpm_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
             "upk_advance_step": (C.c_int, [vp, vp, vp]),
@@ -324,6 +326,12 @@ class Context:
     def ddim_step_cfg(self, x, eps2, coefs, noise, step, pred_x0, xin, ld_xin, batch, c, hw, scale):
         self._chk(self.lib.upk_ddim_step_cfg_f32(self.h, _ptr(x), _ptr(eps2), _ptr(coefs), _ptr(noise), _ptr(step),
                                                  _ptr(pred_x0), _ptr(xin), ld_xin, batch, c, hw, float(scale), self._s()))
+
+    def ddim_step_edit(self, x, eps, coefs, noise, keep, mask, n_rows, step, pred_x0, x_plain, xin, ld_xin, batch, c, hw,
+                       scale=1.0, cfg=False):
+        self._chk(self.lib.upk_ddim_step_edit_f32(self.h, _ptr(x), _ptr(eps), _ptr(coefs), _ptr(noise), _ptr(keep),
+                                                  _ptr(mask), int(n_rows), _ptr(step), _ptr(pred_x0), _ptr(x_plain),
+                                                  _ptr(xin), ld_xin, batch, c, hw, float(scale), int(cfg), self._s()))
 
     def ddpm_step(self, x, model_out, coefs, noise, noise2, x0, mask, step, pred_x0, xin, ld_xin, batch, c, hw, flags):
         self._chk(self.lib.upk_ddpm_step_f32(self.h, _ptr(x), _ptr(model_out), _ptr(coefs), _ptr(noise), _ptr(noise2),

@@ -279,6 +279,44 @@ __global__ void ddim_step_cfg_kernel(float* x, const float* eps2, const float* c
   if (step) step_advance(step, done);
 }
 
+// The DDIM update of the two kernels above for the editing calls (inpainting: ddim.py:144-147; img2img: decode): guidance
+// is an argument (cfg_rows = 2: eps = [uncond ; cond]); with a mask the kernel also applies the reference's blend for the
+// NEXT step, x = mask * keep[st + 1] + (1 - mask) * x_prev (the reference blends before the model evaluation of a step: in
+// a captured step that is the tail of the step before); the last row's result is not blended.  x_plain: the unblended value.
+__global__ void ddim_step_edit_kernel(float* x, const float* eps, const float* coefs, const float* noise, const float* keep,
+                                      const float* mask, int n_rows, const int* step, float* pred_x0, float* x_plain,
+                                      f16* xin, int ld_xin, int c, int hw, long n, int cfg_rows, float scale, int* done) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int st = step ? *step : 0;
+  if (idx < n) {
+    const float* cf = coefs + 4 * st;
+    const float c0 = cf[0], c1 = cf[1], c2 = cf[2], c3 = cf[3];
+    float e = eps[idx];
+    if (cfg_rows == 2) e = e + scale * (eps[n + idx] - e);
+    const float xv = x[idx];
+    const float p0 = (xv - c0 * e) * c1;
+    float xp = c2 * p0 + c3 * e;
+    if (noise) xp += noise[(long)st * n + idx];
+    if (x_plain) x_plain[idx] = xp;
+    if (mask && st + 1 < n_rows) {
+      const float mk = mask[idx];
+      xp = mk * keep[(long)(st + 1) * n + idx] + (1.f - mk) * xp;
+    }
+    x[idx] = xp;
+    if (pred_x0) pred_x0[idx] = p0;
+    if (xin) {
+      const long p = idx % hw;
+      const long t = idx / hw;
+      const long ch = t % c;
+      const long b = t / c;
+      const f16 h = (f16)xp;
+      xin[(b * hw + p) * ld_xin + ch] = h;
+      if (cfg_rows == 2) xin[(n / c + b * hw + p) * ld_xin + ch] = h;  // row offset batch*hw: the conditional half
+    }
+  }
+  if (step) step_advance(step, done);
+}
+
 // One model evaluation of the PLMS sampler (plms.py:177-236), k = *step counts EVALUATIONS (S + 1 for S steps):
 //   k = 0: e0 = eps; pseudo improved Euler predictor: xin <- ddim(x, e0, coef[0]); x itself stays; hist <- e0
 //   k = 1: eps was evaluated at (predictor, t_1): e' = (e0 + eps) / 2; x <- ddim(x, e', coef[0])
@@ -492,6 +530,22 @@ extern "C" int upk_ddim_step_cfg_f32(upk_ctx* ctx, float* x, const float* eps2, 
   hipLaunchKernelGGL(ddim_step_cfg_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, x, eps2,
                      coefs, noise, step, pred_x0, (f16*)xin, ld_xin, c, hw, n, scale, ctx->step_done);
   return upk_check_launch(ctx, "ddim_step_cfg");
+}
+
+extern "C" int upk_ddim_step_edit_f32(upk_ctx* ctx, float* x, const float* eps, const float* coefs, const float* noise,
+                                      const float* keep, const float* mask, int n_rows, const int32_t* step,
+                                      float* pred_x0, float* x_plain, void* xin, int ld_xin, int batch, int c, int hw,
+                                      float scale, int cfg, upk_stream stream_) {
+  if (!ctx) return UPK_EINVAL;
+  if (!x || !eps || !coefs || batch <= 0 || c <= 0 || hw <= 0) return upk_fail(ctx, UPK_EINVAL, "ddim_step_edit: bad args");
+  if (mask && (!keep || n_rows <= 0)) return upk_fail(ctx, UPK_EINVAL, "ddim_step_edit: mask without keep rows");
+  if (xin && ld_xin < c) return upk_fail(ctx, UPK_EINVAL, "ddim_step_edit: ld_xin < c");
+  const long n = (long)batch * c * hw;
+  upk_prof_scope prof(ctx, UPK_CLS_OTHER, (hipStream_t)stream_);
+  hipLaunchKernelGGL(ddim_step_edit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, x, eps,
+                     coefs, noise, keep, mask, n_rows, step, pred_x0, x_plain, (f16*)xin, ld_xin, c, hw, n, cfg ? 2 : 1,
+                     scale, ctx->step_done);
+  return upk_check_launch(ctx, "ddim_step_edit");
 }
 
 extern "C" int upk_plms_step_f32(upk_ctx* ctx, float* x, const float* eps, const float* coefs, const int32_t* step,

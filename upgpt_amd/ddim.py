@@ -8,6 +8,10 @@ step counter increment — is ONE captured HIP graph replayed S times; timestep 
 for all S steps and the cross-attention K/V of the context are computed once before the
 loop.  The reference instead runs ~1-2 k ATen launches plus four torch.full allocations
 per step from Python (ddim.py:140-203).
+
+The editing calls run on the same captured loop (upk_ddim_step_edit_f32): sample(mask=, x0=)
+(inpainting), decode (img2img) and ddim_sampling(timesteps=) — the last two as chains that
+start at a later row of the same S-row tables.
 """
 import contextlib
 import os
@@ -108,15 +112,29 @@ class DDIMSampler(object):
     # ------------------------------------------------------------------ fast path
     def _fast_ok(self, cond, ddim_use_original_steps, quantize_denoised, mask, noise_dropout, score_corrector,
                  ucg_scale, uc):
-        if ddim_use_original_steps or quantize_denoised or mask is not None or noise_dropout > 0. \
-                or score_corrector is not None:
+        # (a mask stays on the fast path: its blend is part of the step kernel, see _fast_sampling)
+        if ddim_use_original_steps or quantize_denoised or noise_dropout > 0. or score_corrector is not None:
             return False
         if uc is not None and ucg_scale != 1. and type(uc) is not type(cond):
             return False
         return hasattr(self.model, "_split_cond") and cond is not None
 
+    def _is_tail(self, timesteps):
+        """`timesteps` is a non-empty prefix of the schedule: a chain over the LAST len(timesteps) loop positions."""
+        n = len(timesteps)
+        return 0 < n <= len(self.ddim_timesteps) and np.array_equal(timesteps, self.ddim_timesteps[:n])
+
     def _fast_sampling(self, cond, shape, x_T, timesteps, callback, img_callback, log_every_t, temperature,
-                       normals_sequence, cfg_scale=1., uc=None):
+                       normals_sequence, cfg_scale=1., uc=None, mask=None, x0=None, edit=False):
+        """`timesteps`: the schedule, or a prefix of it (decode, ddim_sampling(timesteps=)): T = len(timesteps) steps
+        from row S - T of the S-row tables.  mask / x0: inpainting (ddim.py:144-147).  The reference blends
+        q_sample(x0, t) into the latent BEFORE the model evaluation of every step; in the captured loop the step kernel
+        does it for the NEXT step (the first one is blended here), reading row r of the `keep` table = q_sample(x0, t_r),
+        which is filled before the loop by one model.q_sample call per step — each followed by that step's noise draw,
+        so the generator sees the general path's order of draws and an overridden q_sample keeps working.
+        edit: run upk_ddim_step_edit_f32 also without a mask and from row 0.  log_every_t None: nothing is logged."""
+        masked = mask is not None
+        require(not masked or x0 is not None, "mask given without x0", ValueError)
         model = self.model
         unet = model.model.diffusion_model
         b, C, H, W = shape
@@ -124,7 +142,10 @@ class DDIMSampler(object):
         if cfg:  # one UNet pass over [unconditional ; conditional] (ddim.py:173-178), combined in the update kernel
             cond = self._cat_cond(uc, cond)
         c_concat, c_cross = model._split_cond(cond)
-        S = int(timesteps.shape[0])
+        S = int(self.ddim_timesteps.shape[0])  # rows of the tables
+        T = int(timesteps.shape[0])            # steps of this chain ...
+        k = S - T                              # ... which starts at this row
+        timesteps = self.ddim_timesteps
         plan = unet.plan(2 * b if cfg else b, H, W, c_cross.shape[1], S, "sampler")
         dev = plan.dev
         with torch.cuda.device(dev):
@@ -136,7 +157,8 @@ class DDIMSampler(object):
                 setattr(plan, attr, st)
             order = np.arange(S)[::-1].copy()  # loop order: descending DDIM index
             sig = torch.as_tensor(np.asarray(self.ddim_sigmas, dtype=np.float64)).float()[torch.as_tensor(order)]
-            with_noise = bool((sig != 0).any())
+            with_noise = bool((sig[k:] != 0).any())
+            st.edit = "masked" if masked else "plain" if (edit or k > 0) else None
             f64b = lambda v: np.asarray(v, dtype=np.float64).tobytes()
             # upload-once caches.  The timestep rows live on the PLAN (one buffer shared by the DDIM / PLMS, guided / unguided
             # sampler states of that plan), so their key does too; the coefficient table is this state's own
@@ -145,14 +167,18 @@ class DDIMSampler(object):
             fresh_rows = getattr(plan, "_t_rows_key", None) != rkey
             fresh_coefs = getattr(st, "_coef_key", None) != ckey
             fresh = fresh_rows or fresh_coefs
-            on_host = any(t is not None and torch.is_tensor(t) and not t.is_cuda for t in (x_T, c_concat, c_cross))
+            on_host = any(t is not None and torch.is_tensor(t) and not t.is_cuda for t in (x_T, c_concat, c_cross, mask, x0))
             # uploads from the host never overlap another lane's graph capture (_lib.host_io); a call with everything on
             # the device and an unchanged schedule uploads nothing and takes no lock
             with (host_io() if (fresh or on_host or with_noise) else contextlib.nullcontext()):
                 img = torch.randn(shape, device=dev) if x_T is None else x_T.to(dev, torch.float32)
                 st.x.copy_(img)
-                plan.load_sampler_inputs(torch.cat([st.x, st.x]) if cfg else st.x, c_concat, c_cross, unet.in_channels,
-                                         rkey, np.asarray(timesteps)[order].astype(np.float32))
+                if masked:
+                    keep, emask, _ = st.ensure_edit()
+                    x0 = x0.to(dev)
+                    mask = mask.to(dev, torch.float32)
+                    emask.copy_(mask.expand(shape).reshape(-1))
+                    desc = np.asarray(timesteps)[order]
                 if fresh_coefs:
                     st.coefs.copy_(ddim_coefficient_table(self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sigmas,
                                                           self.ddim_sqrt_one_minus_alphas, order))
@@ -161,31 +187,39 @@ class DDIMSampler(object):
                 # sigma_t == 0 (ddim.py:200, util.py:264-267), so after sample() the device generator has advanced by S
                 # draws of the latent's shape — a caller that seeds once and samples several batches (inference.ipynb)
                 # sees the same stream positions.  The S draws happen here, before the captured loop, one call per step.
-                if with_noise:
-                    nz = st.ensure_noise()
-                    if normals_sequence is not None:
-                        ns = normals_sequence if torch.is_tensor(normals_sequence) else torch.stack(
-                            list(normals_sequence))
-                        nz.copy_(ns.to(dev, torch.float32).reshape(S, -1))
-                    else:
-                        for i in range(S):
+                # A masked chain draws q_sample's noise in front of each step's own draw (ddim.py:144-147).
+                nz = st.ensure_noise() if with_noise else None
+                if with_noise and normals_sequence is not None:
+                    ns = normals_sequence if torch.is_tensor(normals_sequence) else torch.stack(list(normals_sequence))
+                    nz[k:].copy_(ns.to(dev, torch.float32).reshape(T, -1))
+                for i in range(k, S):
+                    if masked:
+                        ts = torch.full((b,), int(desc[i]), device=dev, dtype=torch.long)
+                        keep[i].copy_(model.q_sample(x0, ts).to(dev, torch.float32).reshape(-1))
+                    if normals_sequence is None:
+                        if with_noise:
                             nz[i].copy_(torch.randn(shape, device=dev).reshape(-1))
-                    nz.mul_((sig * float(temperature)).to(dev)[:, None])
-                elif normals_sequence is None:
-                    for i in range(S):
-                        torch.randn(shape, device=dev)  # (sigma = 0: the draw is discarded, as in the reference)
-                plan.step.zero_()
+                        else:
+                            torch.randn(shape, device=dev)  # (sigma = 0: the draw is discarded, as in the reference)
+                if with_noise:
+                    nz[k:].mul_((sig[k:] * float(temperature)).to(dev)[:, None])
+                first = st.x.clone()  # (the reference's intermediates start with the unblended x_T)
+                if masked:  # the blend in front of the first step; the step kernel does the later ones
+                    st.x.copy_(keep[k].view(shape) * mask + (1. - mask) * st.x)
+                plan.load_sampler_inputs(torch.cat([st.x, st.x]) if cfg else st.x, c_concat, c_cross, unet.in_channels,
+                                         rkey, np.asarray(timesteps)[order].astype(np.float32))
+                plan.step.fill_(k)
                 plan.prep.run()
-            intermediates = {"x_inter": [st.x.clone()], "pred_x0": [st.x.clone()]}
-            print(f"Running DDIM Sampling with {S} timesteps")
+            intermediates = {"x_inter": [first], "pred_x0": [first.clone()]}
+            print(f"Running DDIM Sampling with {T} timesteps")
             # steps whose result the host looks at (callbacks, logged intermediates: ddim.py:139-147) end a graph; the
             # steps between them run up to STEPS_PER_GRAPH to a graph launch
             watched = callback is not None or img_callback is not None
-            logged = lambda i: (S - i - 1) % log_every_t == 0 or i == 0
+            logged = lambda i: log_every_t is not None and ((T - i - 1) % log_every_t == 0 or i == 0)
             i = 0
-            while i < S:
+            while i < T:
                 n = 1
-                while n < STEPS_PER_GRAPH and i + n < S and not (watched or logged(i + n - 1)):
+                while n < STEPS_PER_GRAPH and i + n < T and not (watched or logged(i + n - 1)):
                     n += 1
                 st.launch(with_noise, cfg_scale, n)
                 i += n
@@ -194,9 +228,10 @@ class DDIMSampler(object):
                 if img_callback:
                     img_callback(st.pred_x0.clone(), i - 1)
                 if logged(i - 1):
-                    intermediates["x_inter"].append(st.x.clone())
+                    # (masked: st.x already holds the blend for the next step; the reference logs the unblended value)
+                    intermediates["x_inter"].append((st.x_plain if masked else st.x).clone())
                     intermediates["pred_x0"].append(st.pred_x0.clone())
-            return st.x.clone(), intermediates
+            return st.x.clone(), intermediates  # (the last step's result is never blended)
 
     # ------------------------------------------------------------------ reference surface
     @torch.no_grad()
@@ -214,10 +249,10 @@ class DDIMSampler(object):
 
         if self._fast_ok(cond, ddim_use_original_steps, quantize_denoised, mask, noise_dropout, score_corrector,
                          unconditional_guidance_scale, unconditional_conditioning) \
-                and len(timesteps) == len(self.ddim_timesteps):
+                and self._is_tail(timesteps):
             return self._fast_sampling(cond, shape, x_T, timesteps, callback, img_callback, log_every_t,
                                        temperature, normals_sequence, cfg_scale=unconditional_guidance_scale,
-                                       uc=unconditional_conditioning)
+                                       uc=unconditional_conditioning, mask=mask, x0=x0)
 
         # general path: one apply_model + one fused update kernel per step, driven from Python
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device)
@@ -337,6 +372,12 @@ class DDIMSampler(object):
         timesteps = np.arange(self.ddpm_num_timesteps) if use_original_steps else self.ddim_timesteps
         timesteps = timesteps[:t_start]
         total_steps = timesteps.shape[0]
+        if self._fast_ok(cond, use_original_steps, False, None, 0., None, unconditional_guidance_scale,
+                         unconditional_conditioning) and self._is_tail(timesteps):
+            # the last total_steps rows of the captured loop; one generator draw per step, as p_sample_ddim makes
+            return self._fast_sampling(cond, tuple(x_latent.shape), x_latent, timesteps, None, None, None, 1., None,
+                                       cfg_scale=unconditional_guidance_scale, uc=unconditional_conditioning,
+                                       edit=True)[0]
         print(f"Running DDIM Sampling with {total_steps} timesteps")
         x_dec = x_latent
         for i, step in enumerate(np.flip(timesteps)):

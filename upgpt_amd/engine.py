@@ -224,7 +224,8 @@ class UNetPlan(Emitter):
 
     # ---- host-facing helpers
     def close(self):
-        """Releases the graphs of the sampler states attached to this plan (ddim.py / plms.py fast paths)."""
+        """Releases the graphs (and the DDIM edit buffers) of the sampler states attached to this plan (ddim.py / plms.py
+        fast paths)."""
         for attr in ("_sampler_state", "_sampler_state_cfg", "_plms_state", "_plms_state_cfg", "_ddpm_state"):
             st = self.__dict__.pop(attr, None)
             if st is not None:
@@ -381,7 +382,12 @@ class VAEEncodePlan(Emitter):
 class SamplerState:
     """Device state of one DDIM run on a sampler-mode UNetPlan: latent x (fp32 NCHW),
     pred_x0, the per-step coefficient / noise tables and the captured step graph
-    (UNet body -> upk_ddim_step_f32 -> upk_advance_step)."""
+    (UNet body -> upk_ddim_step_f32 -> upk_advance_step).
+
+    DDIM edit mode (`edit`, set by the sampler before graph() / launch()): None = the plain generation graphs; "plain" =
+    upk_ddim_step_edit_f32 without a mask (chains that start inside the schedule: decode, a shortened `timesteps`);
+    "masked" = the same kernel with the keep table and the mask (inpainting).  Each has graphs of its own.  A chain
+    that starts at loop position k > 0 only presets plan.step to k: timestep rows and coefficients stay the S-row tables."""
 
     def __init__(self, plan: UNetPlan, channels, cfg=False, plms=False, ddpm=False):
         """cfg: classifier-free guidance — the plan runs 2*B rows ([unconditional ; conditional], ddim.py:173-178),
@@ -399,6 +405,8 @@ class SamplerState:
         self.ddpm = bool(ddpm)
         self.ddpm_flags, self.masked = 0, False  # (the DDPM variant the next graph() / step_eager() runs)
         self.noise2 = self.x0 = self.mask = None
+        self.edit = None  # (the DDIM variant the next graph() runs: None / "plain" / "masked")
+        self.keep = self.edit_mask = self.x_plain = None
         B, H, W, R = (plan.B // 2 if cfg else plan.B), plan.H, plan.W, plan.rows
         self.B = B
         self.C = channels
@@ -419,6 +427,7 @@ class SamplerState:
         for g in self.graphs.values():
             self.plan.ctx.graph_destroy(g)
         self.graphs = {}
+        self.keep = self.edit_mask = self.x_plain = None  # (no graph is left that reads them)
 
     def ensure_noise(self):
         if self.noise is None:
@@ -434,6 +443,17 @@ class SamplerState:
             self.x0 = p.alloc(n, dtype=torch.float32)
             self.mask = p.alloc(n, dtype=torch.float32)
         return self.noise2, self.x0, self.mask
+
+    def ensure_edit(self):
+        """The masked-chain buffers (DDIM): keep [rows, n] (row r = q_sample(x0, t) of loop position r), the mask expanded
+        to the latent, and x_plain (the unblended x_prev the reference logs).  They belong to this state, not to the
+        plan's buffer list: close() frees them.  At 200 steps, B = 8, 4x32x24 the table is 200 * 24576 * 4 B = 20 MB."""
+        if self.keep is None:
+            p, n = self.plan, self.B * self.C * self.plan.H * self.plan.W
+            self.keep = torch.empty(p.rows, n, dtype=torch.float32, device=p.dev)
+            self.edit_mask = torch.empty(n, dtype=torch.float32, device=p.dev)
+            self.x_plain = torch.empty(self.B, self.C, p.H, p.W, dtype=torch.float32, device=p.dev)
+        return self.keep, self.edit_mask, self.x_plain
 
     def _emit_tail(self, stream, with_noise, scale=1.0):
         p = self.plan
@@ -460,6 +480,14 @@ class SamplerState:
                                                p.step.data_ptr(), self.hist.data_ptr(), self.pred_x0.data_ptr(),
                                                p.xin.t.data_ptr(), p.xin.ld, self.B, self.C, p.H * p.W, float(scale),
                                                int(self.cfg), stream))
+        elif self.edit is not None:
+            m = self.edit == "masked"
+            ptr = lambda t: t.data_ptr() if m else None
+            p.ctx._chk(p.lib.upk_ddim_step_edit_f32(p.hctx, self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(), nz,
+                                                    ptr(self.keep), ptr(self.edit_mask), p.rows, p.step.data_ptr(),
+                                                    self.pred_x0.data_ptr(), ptr(self.x_plain), p.xin.t.data_ptr(),
+                                                    p.xin.ld, self.B, self.C, p.H * p.W, float(scale), int(self.cfg),
+                                                    stream))
         elif self.cfg:
             p.ctx._chk(p.lib.upk_ddim_step_cfg_f32(p.hctx, self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(), nz,
                                                    p.step.data_ptr(), self.pred_x0.data_ptr(), p.xin.t.data_ptr(),
@@ -481,6 +509,10 @@ class SamplerState:
         key = (with_noise, float(scale) if self.cfg else 1.0) + ((int(nsteps),) if nsteps != 1 else ())
         if self.ddpm:
             key += ("ddpm", int(self.ddpm_flags), bool(self.masked))
+        elif self.edit is not None:
+            require(self.edit in ("plain", "masked") and not self.plms, "edit mode is 'plain' or 'masked', DDIM only",
+                    ValueError)
+            key += ("edit", self.edit)
         g = self.graphs.pop(key, None)
         if g is not None:
             self.graphs[key] = g  # (most recently used last: eviction takes the least recently used graph)
@@ -490,6 +522,8 @@ class SamplerState:
                 self.ensure_noise()
             if self.masked:
                 self.ensure_mask()
+            if self.edit == "masked":
+                self.ensure_edit()
             with L.host_io():  # (no other lane uploads from the host while this thread captures)
                 side = torch.cuda.Stream(device=p.dev)
                 side.wait_stream(torch.cuda.current_stream(p.dev))
