@@ -541,6 +541,49 @@ long long upk_kernel_launches(upk_ctx* ctx, int reset);
 int upk_advance_step(upk_ctx* ctx, int32_t* step, upk_stream stream);
 
 /* ------------------------------------------------------------------ */
+/* Image finishing: fp32 images -> uint8 HWC pictures (test_step).       */
+/* ------------------------------------------------------------------ */
+/* What LatentDiffusion.test_step does to every image before it is saved (ddpm.py:1352-1357 for the samples, the
+ * reconstruction and the batch's images, ddpm.py:1371-1376 for the style crops; T.CenterCrop, torch.clamp, the
+ * rescale, T.Normalize, torch.cat along the width and T.ToPILImage's pic.mul(255).byte()), one launch per component:
+ * a window of `batch` fp32 3-channel source images is converted and written into a window of a uint8 HWC destination.
+ *   src      [batch] images of src_h x src_w, UPK_LAYOUT_NCHW (3 planes) or UPK_LAYOUT_NHWC (3 interleaved floats),
+ *            src_batch_stride floats apart (>= 3 * src_h * src_w; ignored for batch == 1); 4-byte aligned
+ *   window   rows [top, top + crop_h), columns [left, left + crop_w) of every source image (the centre-crop offsets
+ *            are the caller's: upgpt_amd/evaluate.py center_crop_window)
+ *   dst      byte (c) of pixel (y, x) of sample b goes to dst[b * dst_sample_stride + y * dst_pitch + 3 * (dst_x + x) + c]
+ *            (dst_pitch, dst_sample_stride in bytes, dst_x in pixels): launches with different dst_x lay components
+ *            side by side in one strip, no concatenation pass.  Bytes outside the window are not touched.
+ *   mode     the value t in front of the quantisation, per element v of channel c, every operation ONE correctly
+ *            rounded IEEE fp32 operation in exactly this order (no FMA contraction, no reassociation):
+ *              UPK_FINISH_SAMPLE  t = (min(max(v, -1), 1) + 1) / 2        log["samples"], log["reconstruction"]
+ *              UPK_FINISH_INPUT   t = (v + 1) / 2                         batch["image" / "src_image" / "smpl_image"]
+ *              UPK_FINISH_DENORM  t = (v / d[c]) - m[c]                   batch["styles"] crops (CLIP-normalised)
+ *            denorm_host: HOST array {d[0], d[1], d[2], m[0], m[1], m[2]}, read before the call returns (DENORM only,
+ *            else may be NULL); the reference's values are d = float32(1 / 0.226862954, 1 / 0.26130258,
+ *            1 / 0.27577711) (quotients formed in double, then rounded, as T.Normalize does with its std list) and
+ *            m = float32(-0.48145466, -0.4578275, -0.40821073).
+ *   byte     u = (uint8) trunc(t * 255), saturated to [0, 255], NaN -> 0.
+ * For inputs in the documented ranges ([-1, 1] for INPUT, CLIP-normalised [0, 1] images for DENORM, anything for
+ * SAMPLE) these are bit for bit the bytes of the reference's torch expression followed by ToPILImage.  Outside them
+ * t * 255 leaves [0, 256) and the reference's .byte() is undefined behaviour (it wraps on some hosts); this entry
+ * point SATURATES instead.
+ * Errors (UPK_EINVAL): null src / dst, src not 4-byte aligned, unknown layout / mode, non-positive sizes, a window
+ * outside the source, (dst_x + crop_w) * 3 > dst_pitch, overlapping samples (a stride smaller than one sample's
+ * extent), DENORM without denorm_host or with d = 0 / non-finite values.  Sources, offsets and strides that are
+ * multiples of 4 pixels (16-byte aligned src, 4-byte aligned dst) take 16-byte loads and dword stores; everything else
+ * is handled per pixel with the same results.  Never allocates, never synchronises, graph-capturable. */
+#define UPK_LAYOUT_NCHW 0
+#define UPK_LAYOUT_NHWC 1
+#define UPK_FINISH_SAMPLE 0
+#define UPK_FINISH_INPUT 1
+#define UPK_FINISH_DENORM 2
+int upk_image_finish_u8(upk_ctx* ctx, const float* src, int layout, int batch, int src_h, int src_w,
+                        long long src_batch_stride, int top, int left, int crop_h, int crop_w, uint8_t* dst,
+                        long long dst_pitch, int dst_x, long long dst_sample_stride, int mode,
+                        const float* denorm_host, upk_stream stream);
+
+/* ------------------------------------------------------------------ */
 /* CU-partitioned streams (execution lanes on disjoint CU sets).         */
 /* The reference has no counterpart: it runs one batch on `cuda:0`       */
 /* (app.py:21); lanes are this build's serving mode. */

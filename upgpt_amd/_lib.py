@@ -27,6 +27,7 @@ SYMBOLS = [
     "upk_nchw_f32_to_nhwc_f16", "upk_nhwc_f16_to_nchw_f32", "upk_f32_to_f16", "upk_ddim_step_f32",
     "upk_ddim_step_cfg_f32", "upk_ddim_step_edit_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
     "upk_patchify_nchw_f32_f16", "upk_vit_assemble_f16", "upk_gather_rows_f16",
+    "upk_image_finish_u8",
     "upk_advance_step", "upk_step_autoadvance", "upk_kernel_launches", "upk_graph_begin", "upk_graph_end", "upk_graph_launch", "upk_graph_destroy",
     "upk_prof_enable", "upk_prof_collect",
     "upk_stream_create_cumask", "upk_stream_destroy", "upk_probe_placement", "upk_probe_clock",
@@ -34,6 +35,8 @@ SYMBOLS = [
 
 F_SILU, F_GEGLU, F_OUT_F32, F_OUT_NCHW_F32, F_UPSAMPLE2X, F_PAD_ASYM = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 DDPM_X0, DDPM_CLIP = 0x1, 0x2  # upk_ddpm_step_f32 flags
+LAYOUT_NCHW, LAYOUT_NHWC = 0, 1  # upk_image_finish_u8 source layouts
+FINISH_SAMPLE, FINISH_INPUT, FINISH_DENORM = 0, 1, 2  # ... and arithmetic modes
 F_QUICKGELU = 0x40
 NUM_CLASSES = 5
 CLASS_NAMES = ["igemm", "attention", "groupnorm", "layernorm", "other"]
@@ -179,6 +182,8 @@ def load_library(path=None):
                                                  i32, vp]),
             "upk_plms_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),
             "upk_ddpm_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+            "upk_image_finish_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i64, i32, i32, i32, i32, vp, i64, i32, i64, i32,
+                                              C.POINTER(C.c_float), vp]),
             "upk_advance_step": (C.c_int, [vp, vp, vp]),
             "upk_step_autoadvance": (C.c_int, [vp, vp]),
             "upk_kernel_launches": (C.c_longlong, [vp, i32]),
@@ -342,6 +347,14 @@ class Context:
         self._chk(self.lib.upk_plms_step_f32(self.h, _ptr(x), _ptr(eps), _ptr(coefs), _ptr(step), _ptr(hist),
                                              _ptr(pred_x0), _ptr(xin), ld_xin, batch, c, hw, float(cfg_scale), int(cfg),
                                              self._s()))
+
+    def image_finish(self, src, layout, batch, src_h, src_w, src_bs, top, left, crop_h, crop_w, dst, pitch, dst_x,
+                     dst_bs, mode, denorm=None):
+        """upk_image_finish_u8; denorm: the six host floats {d0, d1, d2, m0, m1, m2} of FINISH_DENORM."""
+        dm = None if denorm is None else (C.c_float * 6)(*[float(v) for v in denorm])
+        self._chk(self.lib.upk_image_finish_u8(self.h, _ptr(src), int(layout), int(batch), int(src_h), int(src_w),
+                                               int(src_bs), int(top), int(left), int(crop_h), int(crop_w), _ptr(dst),
+                                               int(pitch), int(dst_x), int(dst_bs), int(mode), dm, self._s()))
 
     def step_autoadvance(self, done):
         """Arms (done: zeroed device int32) or disarms (None) the step kernels' own increment of *step."""

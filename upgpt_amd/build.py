@@ -13,14 +13,17 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.environ.get("UPK_LIB") or os.path.join(HERE, "libupk.so")  # (UPK_LIB + UPK_CXXFLAGS: dev builds)
-SOURCES = ["igemm.hip", "bigtile.hip", "astat.hip", "mlp.hip", "xblock.hip", "attention.hip", "norm.hip", "misc.hip"]
+SOURCES = ["igemm.hip", "bigtile.hip", "astat.hip", "mlp.hip", "xblock.hip", "attention.hip", "norm.hip", "misc.hip", "image.hip"]
 # per-file flags.  attention.hip: MFMA results straight into arch VGPRs — the softmax between the two matmuls reads
 # every score with VALU instructions, and with the accumulators in AGPRs 112 of ~600 issue slots per 64-key tile were
 # v_accvgpr moves (the kernels use < 128 registers, there is nothing to gain from the AGPR file)
 # -fno-honor-nans -mno-amdgpu-ieee: fmaxf on MFMA results otherwise quiets every operand first (v_max x, x) — two of
 # three instructions of the running-maximum tree; the kernels never produce a NaN (masked scores are -inf, every tile
 # has a visible key per row, so no inf - inf) and infinities keep their meaning
-FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans", "-mno-amdgpu-ieee"]}
+# image.hip: its results are truncated to bytes and specified operation by operation (include/upk.h,
+# upk_image_finish_u8): no mul + add may be contracted into an FMA
+FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans", "-mno-amdgpu-ieee"],
+              "image.hip": ["-ffp-contract=off"]}
 ARCH = "gfx950"
 
 

@@ -5,7 +5,7 @@ What is CONTRACT here (and therefore kept name for name): the constructor keywor
 block of configs/deepfashion/bbox.yaml instantiates unchanged; the module / buffer names that make reference
 checkpoints load (model.diffusion_model.*, model_ema.*, first_stage_model.*, cond_stage_model.*, extra_cond_models.*,
 the schedule buffers); the methods the named callers use (apply_model, decode_first_stage, get_learned_conditioning,
-ema_scope, q_sample, sample_log, log_images, get_input) with their argument order and return shapes.  Everything
+ema_scope, q_sample, sample_log, log_images, test_step, get_input) with their argument order and return shapes.  Everything
 else is this package's own: the schedule buffers come out of one table, conditioning assembly lives in one place
 (`_conditioning`), EMA evaluation packs the shadow weights instead of copying them over the live ones, and the
 training-side state of the reference (loss weights, log-variance, ELBO terms, LR scheduler config) does not exist —
@@ -479,3 +479,24 @@ class LatentDiffusion(AncestralSampling, DDPM):
         if return_keys and any(k in log for k in return_keys):
             return {k: log[k] for k in return_keys}
         return log
+
+    @torch.no_grad()
+    def test_step(self, batch, batch_idx, **log_kwargs):
+        """ddpm.py:1327-1377 — what trainer.test runs per batch (main.py:798): sample the batch through log_images and
+        write results/{samples,concats,styles,gt,recon,src,smpl}/<fname>.jpg under self.logger.save_dir (a Lightning
+        logger, or evaluate.ResultDir(path); without one: ValueError).  Per sample: the generated image, the
+        reconstruction, the target, source and SMPL images, all centre-cropped to crop_size (an image smaller than
+        crop_size: ValueError, torchvision would zero-pad), their strip src | sample | recon | smpl, and the strip of the
+        sample's CLIP-de-normalised style crops (not cropped).  The pictures are finished on the device
+        (evaluate.finished_arrays: upk_image_finish_u8 into one uint8 buffer, one copy, one synchronise) and encoded by
+        PIL with its default JPEG settings.  Returns None.
+        log_images is called with N=len(batch), as the reference calls it: len of the batch DICT, the number of its
+        KEYS, not of its samples — that many samples are produced at most, and (through zip) that many per-sample files
+        written; the styles strips are written for every fname.  Kept as it is.  `log_kwargs` (ddim_steps=50,
+        ddim_eta=0., seed=...) is this package's extension, laid over the reference's arguments
+        (unconditional_guidance_scale=3.0, unconditional_guidance_label=["txt"], use_ema=self.use_ema); without it
+        log_images' defaults apply, 200 DDIM steps at eta 1, as in the reference.
+        NOT reproduced: the reference replaces batch["image" / "src_image" / "smpl_image"] by their cropped, rescaled
+        NCHW tensors in place; the batch is left as it came."""
+        from . import evaluate
+        return evaluate.test_step(self, batch, batch_idx, **log_kwargs)

@@ -1,0 +1,182 @@
+"""LatentDiffusion.test_step (ddpm.py:1327-1377): a test batch -> results/{samples,concats,styles,gt,recon,src,smpl}.
+
+The reference finishes every image on the host with a chain of torch / torchvision element-wise ops (centre crop,
+clamp, rescale, CLIP de-normalisation, width concat, ToPILImage's mul(255).byte()).  Here all of it is
+upk_image_finish_u8 (include/upk.h) on the current stream, writing uint8 HWC pictures into ONE device buffer per call;
+that buffer crosses to pinned host memory in one copy behind one synchronise, and PIL encodes what arrives.  The
+arithmetic contract (one correctly rounded fp32 operation at a time, in the reference's order; truncation; saturation
+where the reference's .byte() is undefined) is stated in include/upk.h and DESIGN.md 16.
+"""
+import os
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._check import require
+
+FOLDERS = ("samples", "concats", "styles", "gt", "recon", "src", "smpl")
+CONCAT_ORDER = ("src", "samples", "recon", "smpl")  # ddpm.py:1362, left to right
+# T.Normalize(mean=0, std=[1 / s]) then T.Normalize(mean=[-m], std=1) (ddpm.py:1330-1331): v / d - m with the quotient
+# 1 / s formed in Python double and rounded to fp32, as T.Normalize does with its std list.  (0.226862954 is the
+# reference's own first constant.)
+DENORM_D = tuple(np.float32(1 / s) for s in (0.226862954, 0.26130258, 0.27577711))
+DENORM_M = tuple(np.float32(-m) for m in (0.48145466, 0.4578275, 0.40821073))
+# log_images arguments of the reference's test_step (ddpm.py:1348-1350); N is added per batch
+LOG_DEFAULTS = dict(unconditional_guidance_scale=3.0, unconditional_guidance_label=["txt"])
+
+
+class ResultDir:
+    """The one attribute test_step reads of a Lightning logger, for callers without Lightning: model.logger =
+    ResultDir(path)."""
+
+    def __init__(self, save_dir):
+        self.save_dir = str(save_dir)
+
+
+def center_crop_window(h, w, crop_size):
+    """(top, left, crop_h, crop_w) of torchvision's CenterCrop(crop_size) on an h x w image: top = int(round((h -
+    crop_h) / 2.0)) with Python's round (x.5 goes to the even neighbour), likewise left.  crop_size: an int (square) or
+    [crop_h, crop_w].  An image smaller than the crop is REFUSED (ValueError): torchvision would zero-pad it first, no
+    UPGPT config asks for that."""
+    if isinstance(crop_size, (int, np.integer)):
+        ch = cw = int(crop_size)
+    else:
+        size = [int(v) for v in crop_size]
+        require(len(size) in (1, 2), "crop_size must be an int or [h, w], got %r" % (crop_size,), ValueError)
+        ch, cw = size[0], size[-1]
+    require(ch > 0 and cw > 0, "crop_size must be positive, got %r" % (crop_size,), ValueError)
+    require(h >= ch and w >= cw, "image %d x %d is smaller than crop_size %d x %d (the zero padding torchvision's "
+            "CenterCrop would add is not supported)" % (h, w, ch, cw), ValueError)
+    return int(round((h - ch) / 2.0)), int(round((w - cw) / 2.0)), ch, cw
+
+
+def finish_images(src, dst, layout, mode, window=None, dst_x=0, denorm=None):
+    """One upk_image_finish_u8 launch on the current stream.
+    src: fp32 device tensor, [B, 3, H, W] (layout _lib.LAYOUT_NCHW) or [B, H, W, 3] (LAYOUT_NHWC); each sample dense,
+    any batch stride.  window: (top, left, crop_h, crop_w) of the source, default the whole image.
+    dst: uint8 device tensor [B, rows >= crop_h, width, 3], pixels dense inside a row (any row pitch / sample stride);
+    columns [dst_x, dst_x + crop_w) of its first crop_h rows are written, nothing else.
+    mode: _lib.FINISH_SAMPLE / FINISH_INPUT / FINISH_DENORM; denorm: (d, m) per-channel triples, default the CLIP
+    constants of the reference.  No CPU fallback: host tensors raise."""
+    require(torch.is_tensor(src) and torch.is_tensor(dst) and src.is_cuda and dst.is_cuda,
+            "finish_images needs device tensors: there is no CPU fallback for the HIP path", RuntimeError)
+    require(src.dtype == torch.float32 and src.dim() == 4, "finish_images: src must be a 4-d fp32 tensor", TypeError)
+    require(dst.dtype == torch.uint8 and dst.dim() == 4 and dst.shape[3] == 3, "finish_images: dst must be uint8 [B, H, W, 3]",
+            TypeError)
+    nhwc = layout == _lib.LAYOUT_NHWC
+    b, (h, w) = src.shape[0], (src.shape[1:3] if nhwc else src.shape[2:4])
+    require(src.shape[3 if nhwc else 1] == 3, "finish_images: 3-channel images only, got %s" % (tuple(src.shape),), ValueError)
+    require(src[0].is_contiguous() and src.stride(0) >= 0, "finish_images: every source sample must be dense", ValueError)
+    require(dst.stride(3) == 1 and dst.stride(2) == 3, "finish_images: dst pixels must be dense inside a row", ValueError)
+    top, left, ch, cw = (0, 0, h, w) if window is None else window
+    require(dst.shape[0] == b and dst.shape[1] >= ch and dst_x >= 0 and dst_x + cw <= dst.shape[2],
+            "finish_images: window %s at x = %d does not fit dst %s" % ((top, left, ch, cw), dst_x, tuple(dst.shape)), ValueError)
+    dm = None
+    if mode == _lib.FINISH_DENORM:
+        d, m = (DENORM_D, DENORM_M) if denorm is None else denorm
+        dm = list(d) + list(m)
+    _lib.get_context(src.device).image_finish(src, layout, b, h, w, src.stride(0), top, left, ch, cw, dst, dst.stride(1),
+                                              dst_x, dst.stride(0), mode, dm)
+
+
+def _sections(n, ch, cw, styles_shape):
+    """name -> (byte offset, shape) of the uint8 pictures inside the one buffer (offsets multiples of 16)."""
+    bs, s, _, sh, sw = styles_shape
+    shapes = [(k, (n, ch, cw, 3)) for k in ("samples", "recon", "gt", "src", "smpl")]
+    shapes += [("concats", (n, ch, len(CONCAT_ORDER) * cw, 3)), ("styles", (bs, sh, s * sw, 3))]
+    out, off = {}, 0
+    for k, shp in shapes:
+        out[k] = (off, shp)
+        off += (int(np.prod(shp)) + 15) // 16 * 16
+    return out, off
+
+
+def finished_arrays(model, batch, log):
+    """The device part of test_step: {samples, recon, gt, src, smpl, concats, styles} -> uint8 host arrays ([n, crop_h,
+    crop_w, 3]; concats [n, crop_h, 4 crop_w, 3] = src | sample | recon | smpl; styles [B, 224, S 224, 3], the crops of
+    a sample side by side, not centre-cropped).  n = the number of images log_images returned, B = the batch's.
+    Every picture is written by upk_image_finish_u8 launches on the current stream into one uint8 device buffer, which
+    is copied to pinned host memory once, behind one synchronise; no fp32 image goes to the host and no torch
+    element-wise op touches a pixel."""
+    dev = model.device
+    samples, recon = log["samples"], log["reconstruction"]
+    n = int(samples.shape[0])
+    require(recon.shape == samples.shape, "reconstruction %s and samples %s differ in shape" % (
+        tuple(recon.shape), tuple(samples.shape)), ValueError)
+    win = center_crop_window(samples.shape[2], samples.shape[3], model.crop_size)
+    ch, cw = win[2], win[3]
+    nchw, nhwc = _lib.LAYOUT_NCHW, _lib.LAYOUT_NHWC
+    comps = {"samples": (samples.to(dev, torch.float32), nchw, _lib.FINISH_SAMPLE, win),
+             "recon": (recon.to(dev, torch.float32), nchw, _lib.FINISH_SAMPLE, win)}
+    for name, key in (("gt", "image"), ("src", "src_image"), ("smpl", "smpl_image")):
+        x = batch[key]
+        require(x.dim() == 4 and x.shape[0] >= n and x.shape[3] == 3, "batch[%r] must be [B >= %d, H, W, 3], got %s" % (
+            key, n, tuple(x.shape)), ValueError)
+        comps[name] = (x[:n].to(dev, torch.float32).contiguous(), nhwc, _lib.FINISH_INPUT,
+                       center_crop_window(x.shape[1], x.shape[2], model.crop_size))
+    styles = batch["styles"]
+    require(styles.dim() == 5 and styles.shape[2] == 3, "batch['styles'] must be [B, S, 3, H, W] image crops, got %s" % (
+        tuple(styles.shape),), ValueError)
+    styles = styles.to(dev, torch.float32).contiguous()
+    sect, total = _sections(n, ch, cw, tuple(styles.shape))
+    buf = torch.empty(total, dtype=torch.uint8, device=dev)
+    view = {k: buf[off:off + int(np.prod(shp))].view(shp) for k, (off, shp) in sect.items()}
+    for name, (src, layout, mode, w) in comps.items():  # every component on its own ...
+        finish_images(src, view[name], layout, mode, window=w)
+    for slot, name in enumerate(CONCAT_ORDER):  # ... and into its slot of the strip: the width concat
+        src, layout, mode, w = comps[name]
+        finish_images(src, view["concats"], layout, mode, window=w, dst_x=slot * cw)
+    for s in range(styles.shape[1]):
+        finish_images(styles[:, s], view["styles"], nchw, _lib.FINISH_DENORM, dst_x=s * styles.shape[4])
+    host = torch.empty(total, dtype=torch.uint8, pin_memory=buf.is_cuda)
+    host.copy_(buf, non_blocking=True)
+    if buf.is_cuda:
+        torch.cuda.current_stream(dev).synchronize()
+    arr = host.numpy()
+    return {k: arr[off:off + int(np.prod(shp))].reshape(shp) for k, (off, shp) in sect.items()}
+
+
+def test_step(model, batch, batch_idx, **log_kwargs):
+    """LatentDiffusion.test_step (see its docstring)."""
+    from PIL import Image
+    save_dir = getattr(getattr(model, "logger", None), "save_dir", None)
+    require(save_dir is not None, "test_step writes under model.logger.save_dir, and this model has no logger with a "
+            "save_dir: set model.logger = upgpt_amd.evaluate.ResultDir(path) (or use evaluate.run_test)", ValueError)
+    roots = {k: Path(save_dir) / "results" / k for k in FOLDERS}
+    for r in roots.values():
+        os.makedirs(str(r), exist_ok=True)
+    kw = dict(LOG_DEFAULTS, N=len(batch), use_ema=model.use_ema)
+    kw.update(log_kwargs)
+    with torch.no_grad():
+        log = model.log_images(batch, **kw)
+        arrays = finished_arrays(model, batch, log)
+    names = list(batch["fname"])
+    per_sample = [k for k in FOLDERS if k != "styles"]
+    for i, fname in zip(range(arrays["samples"].shape[0]), names):
+        for k in per_sample:
+            Image.fromarray(arrays[k][i]).save(roots[k] / f"{fname}.jpg")
+    for fname, strip in zip(names, arrays["styles"]):  # (every fname: this loop is not capped by N)
+        Image.fromarray(strip).save(roots["styles"] / f"{fname}.jpg")
+    return None
+
+
+test_step.__test__ = False  # (not a pytest test, whatever imports it)
+
+
+def run_test(model, batches, save_dir, **log_kwargs):
+    """What trainer.test(model, data) does with test_step (main.py:798), without Lightning: model.logger =
+    ResultDir(save_dir) for the duration, then test_step(batch, i, **log_kwargs) per batch.  Serial: the batches are
+    not spread over execution lanes (log_images draws from the process-wide device generator)."""
+    had, prev = "logger" in vars(model), vars(model).get("logger")
+    model.logger = ResultDir(save_dir)
+    try:
+        for i, batch in enumerate(batches):
+            model.test_step(batch, i, **log_kwargs)
+    finally:
+        if had:
+            model.logger = prev
+        else:
+            del model.logger
+    return Path(save_dir) / "results"
