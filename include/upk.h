@@ -584,6 +584,41 @@ int upk_image_finish_u8(upk_ctx* ctx, const float* src, int layout, int batch, i
                         const float* denorm_host, upk_stream stream);
 
 /* ------------------------------------------------------------------ */
+/* SSIM / MS-SSIM moments of uint8 picture pairs (evaluation metrics).   */
+/* ------------------------------------------------------------------ */
+/* The per-image arithmetic of scripts/eval_metrics.py:110-111 (pytorch_msssim.ssim / ms_ssim with data_range=1,
+ * size_average=False) up to the per-channel means.  Pictures are uint8 HWC, 3 interleaved bytes per pixel, X = u / 255
+ * (T.ToTensor), every channel on its own:
+ *   window     g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)), i = 0..10, normalised to sum 1; applied separably along H then W,
+ *              "valid" (no padding): a level of h x w gives an (h - 10) x (w - 10) map
+ *   moments    mu1 = G*X, mu2 = G*Y, s11 = G*(X X) - mu1^2, s22 = G*(Y Y) - mu2^2, s12 = G*(X Y) - mu1 mu2
+ *   maps       cs_map = (2 s12 + C2) / (s11 + s22 + C2), ssim_map = ((2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1)) cs_map,
+ *              C1 = 0.01^2, C2 = 0.03^2
+ *   means      ssim_c, cs_c = the means of ssim_map, cs_map per (sample, channel)
+ *   next level both pictures through avg_pool2d(kernel 2, stride 2, padding = size % 2 per axis, count_include_pad=True):
+ *              an odd axis s becomes (s + 1) / 2, output i averages inputs 2 i - 1 and 2 i with index -1 reading zero,
+ *              the divisor is always 4 (so a level-l plane is an exact integer sum over 255 * 4^l)
+ * out[((n * levels + l) * 3 + c) * 2 + {0, 1}] = {ssim_c, cs_c} of sample n, level l, channel c (fp32).  What is left
+ * acts on these 6 * levels numbers per image and is the caller's (upgpt_amd/metrics.py): SSIM = the mean over c of ssim_c
+ * at level 0 (no relu); MS-SSIM (levels = 5, needs min(h, w) > 160) = the mean over c of prod_{l<4} relu(cs_c[l])^wt[l] *
+ * relu(ssim_c[4])^wt[4], wt = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333).
+ *   a, b       byte (c) of pixel (y, x) of sample n is at base[n * sample_stride + y * pitch + 3 x + c] (strides in bytes):
+ *              a window of a wider strip or of a larger buffer is compared in place
+ *   levels     1..5; every level must have both sides >= 11, else UPK_ESHAPE
+ *   ws         upk_ssim_ws_bytes(batch, h, w, levels) bytes (0 for arguments upk_ssim_u8 would refuse), 16-byte aligned:
+ *              the pooled planes of the deeper levels and one slot of partial sums per workgroup
+ * Deterministic: no float atomics, every workgroup writes its own slot and a fixed-order pass sums them, so reruns are
+ * bit-identical and a sample's result depends neither on its position in the batch nor on the batch size.
+ * Errors: UPK_EINVAL for null pointers, non-positive sizes, levels outside 1..5, pitch < 3 w, overlapping samples
+ * (batch > 1 and a sample stride below (h - 1) pitch + 3 w), out not 4-byte or ws not 16-byte aligned; UPK_ESHAPE as
+ * above; UPK_EWORKSPACE for ws_bytes below upk_ssim_ws_bytes.  2 levels launches (levels level kernels, levels - 1
+ * pooling kernels, one final pass), all counted in class "other".  Never allocates, never synchronises, graph-capturable. */
+size_t upk_ssim_ws_bytes(int batch, int h, int w, int levels);
+int upk_ssim_u8(upk_ctx* ctx, const uint8_t* a, long long a_pitch, long long a_sample_stride, const uint8_t* b,
+                long long b_pitch, long long b_sample_stride, int batch, int h, int w, int levels, float* out, void* ws,
+                size_t ws_bytes, upk_stream stream);
+
+/* ------------------------------------------------------------------ */
 /* CU-partitioned streams (execution lanes on disjoint CU sets).         */
 /* The reference has no counterpart: it runs one batch on `cuda:0`       */
 /* (app.py:21); lanes are this build's serving mode. */

@@ -27,7 +27,7 @@ SYMBOLS = [
     "upk_nchw_f32_to_nhwc_f16", "upk_nhwc_f16_to_nchw_f32", "upk_f32_to_f16", "upk_ddim_step_f32",
     "upk_ddim_step_cfg_f32", "upk_ddim_step_edit_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
     "upk_patchify_nchw_f32_f16", "upk_vit_assemble_f16", "upk_gather_rows_f16",
-    "upk_image_finish_u8",
+    "upk_image_finish_u8", "upk_ssim_ws_bytes", "upk_ssim_u8",
     "upk_advance_step", "upk_step_autoadvance", "upk_kernel_launches", "upk_graph_begin", "upk_graph_end", "upk_graph_launch", "upk_graph_destroy",
     "upk_prof_enable", "upk_prof_collect",
     "upk_stream_create_cumask", "upk_stream_destroy", "upk_probe_placement", "upk_probe_clock",
@@ -184,6 +184,8 @@ def load_library(path=None):
             "upk_ddpm_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
             "upk_image_finish_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i64, i32, i32, i32, i32, vp, i64, i32, i64, i32,
                                               C.POINTER(C.c_float), vp]),
+            "upk_ssim_ws_bytes": (C.c_size_t, [i32, i32, i32, i32]),
+            "upk_ssim_u8": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, vp, vp, C.c_size_t, vp]),
             "upk_advance_step": (C.c_int, [vp, vp, vp]),
             "upk_step_autoadvance": (C.c_int, [vp, vp]),
             "upk_kernel_launches": (C.c_longlong, [vp, i32]),
@@ -355,6 +357,15 @@ class Context:
         self._chk(self.lib.upk_image_finish_u8(self.h, _ptr(src), int(layout), int(batch), int(src_h), int(src_w),
                                                int(src_bs), int(top), int(left), int(crop_h), int(crop_w), _ptr(dst),
                                                int(pitch), int(dst_x), int(dst_bs), int(mode), dm, self._s()))
+
+    def ssim_ws_bytes(self, batch, h, w, levels):
+        return self.lib.upk_ssim_ws_bytes(int(batch), int(h), int(w), int(levels))
+
+    def ssim_u8(self, a, a_pitch, a_ss, b, b_pitch, b_ss, batch, h, w, levels, out, ws, ws_bytes):
+        """upk_ssim_u8: out [batch, levels, 3, 2] fp32 = (ssim_c, cs_c) per level; pitches / sample strides in bytes."""
+        self._chk(self.lib.upk_ssim_u8(self.h, _ptr(a), int(a_pitch), int(a_ss), _ptr(b), int(b_pitch), int(b_ss),
+                                       int(batch), int(h), int(w), int(levels), _ptr(out), _ptr(ws), int(ws_bytes),
+                                       self._s()))
 
     def step_autoadvance(self, done):
         """Arms (done: zeroed device int32) or disarms (None) the step kernels' own increment of *step."""

@@ -6,6 +6,10 @@ upk_image_finish_u8 (include/upk.h) on the current stream, writing uint8 HWC pic
 that buffer crosses to pinned host memory in one copy behind one synchronise, and PIL encodes what arrives.  The
 arithmetic contract (one correctly rounded fp32 operation at a time, in the reference's order; truncation; saturation
 where the reference's .byte() is undefined) is stated in include/upk.h and DESIGN.md 16.
+
+run_metrics is the step after it (scripts/eval_metrics.py): results/gt against results/samples -> metrics.csv and
+metrics.txt with per-image SSIM and MS-SSIM from upk_ssim_u8 (upgpt_amd/metrics.py, DESIGN.md 17);
+`python -m upgpt_amd.evaluate --dir <save_dir>/results` runs it.
 """
 import os
 from pathlib import Path
@@ -180,3 +184,109 @@ def run_test(model, batches, save_dir, **log_kwargs):
         else:
             del model.logger
     return Path(save_dir) / "results"
+
+
+def _decode(path):
+    """uint8 [H, W, 3] of an image file, or None when it cannot be read."""
+    from PIL import Image
+    try:
+        with Image.open(str(path)) as im:
+            return np.asarray(im.convert("RGB"), dtype=np.uint8)
+    except Exception:
+        return None
+
+
+def run_metrics(results_dir=None, gt_dir=None, sample_dir=None, batch_size=100, device=None):
+    """scripts/eval_metrics.py's SSIM and MS-SSIM columns (its lines 110-111) for a results tree.  LPIPS and FID are not
+    computed.
+
+    gt_dir / sample_dir default to results_dir/gt and results_dir/samples.  Every *.jpg / *.png of sample_dir is paired
+    with the file of the same name in gt_dir, decoded by PIL, grouped by picture size and sent to the device in batches of
+    batch_size; each batch is one metrics.ssim_levels call and ONE device -> host copy (6 * levels floats per picture).
+    Writes metrics.csv (columns name, SSIM, MSSIM; rows in name order) and metrics.txt (SSIM: <mean>, MSSIM: <mean>)
+    into the parent of sample_dir, where the reference puts them, and returns {"SSIM": mean, "MSSIM": mean, "n": rows,
+    "skipped": [names]}.
+
+    MSSIM is NaN for a picture whose smaller side is <= 160 (ms_ssim is undefined there), and its mean ignores those.
+    One behaviour of the reference is deliberately NOT reproduced: its loader substitutes the NEXT sample for a pair it
+    cannot read, so that pair's neighbour is counted twice.  Here a sample without a readable ground truth of the same
+    size (or smaller than the 11-tap window) goes into "skipped" and is left out of both files and both means."""
+    import csv
+
+    from . import metrics
+    require(results_dir is not None or (gt_dir and sample_dir), "run_metrics needs results_dir, or gt_dir and sample_dir", ValueError)
+    gt_dir = Path(gt_dir) if gt_dir else Path(results_dir) / "gt"
+    sample_dir = Path(sample_dir) if sample_dir else Path(results_dir) / "samples"
+    require(gt_dir.is_dir() and sample_dir.is_dir(), "run_metrics: %s and %s must be directories" % (gt_dir, sample_dir), ValueError)
+    batch_size = int(batch_size)
+    require(batch_size >= 1, "batch_size must be positive", ValueError)
+    if device is None:  # (without a GPU metrics.ssim_levels refuses the host tensors: there is no CPU fallback)
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    nl = len(metrics.MS_WEIGHTS)
+    rows, skipped, pending = {}, [], {}
+
+    def flush(size):
+        names, gts, smps = pending.pop(size)
+        deep = min(size) > metrics.MS_MIN_SIDE
+        a = torch.from_numpy(np.stack(smps)).to(device, non_blocking=True)
+        b = torch.from_numpy(np.stack(gts)).to(device, non_blocking=True)
+        with torch.no_grad():
+            lv = metrics.ssim_levels(a, b, nl if deep else 1).cpu()  # the one device -> host copy of the batch
+        s = metrics.ssim_from_levels(lv).tolist()
+        m = metrics.ms_ssim_from_levels(lv).tolist() if deep else [float("nan")] * len(names)
+        rows.update({n: (si, mi) for n, si, mi in zip(names, s, m)})
+
+    for name in sorted(f.name for f in sample_dir.iterdir() if f.suffix in (".jpg", ".png") and f.is_file()):
+        smp = _decode(sample_dir / name)
+        gt = _decode(gt_dir / name) if (gt_dir / name).is_file() else None
+        if smp is None or gt is None or smp.shape != gt.shape or min(smp.shape[:2]) < metrics.WINDOW:
+            skipped.append(name)
+            continue
+        group = pending.setdefault(smp.shape[:2], ([], [], []))
+        for lst, v in zip(group, (name, gt, smp)):
+            lst.append(v)
+        if len(group[0]) >= batch_size:
+            flush(smp.shape[:2])
+    for size in list(pending):
+        flush(size)
+
+    names = sorted(rows)
+    ssim_vals = np.array([rows[n][0] for n in names], dtype=np.float64)
+    ms_vals = np.array([rows[n][1] for n in names], dtype=np.float64)
+    ms_ok = ms_vals[~np.isnan(ms_vals)]
+    means = {"SSIM": float(ssim_vals.mean()) if len(names) else float("nan"),
+             "MSSIM": float(ms_ok.mean()) if ms_ok.size else float("nan")}
+    log_dir = sample_dir.resolve().parent
+    with open(str(log_dir / "metrics.csv"), "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(["name", "SSIM", "MSSIM"])
+        for n in names:
+            wr.writerow([n, repr(rows[n][0]), repr(rows[n][1])])
+    with open(str(log_dir / "metrics.txt"), "w") as f:
+        for k in ("SSIM", "MSSIM"):
+            f.write("%s: %r\n" % (k, means[k]))
+    return dict(means, n=len(names), skipped=skipped)
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m upgpt_amd.evaluate", description="SSIM / MS-SSIM of a results tree "
+                                 "(gt against samples) -> metrics.csv, metrics.txt next to the samples folder")
+    ap.add_argument("--dir", default=None, help="results directory holding gt/ and samples/")
+    ap.add_argument("--gt_dir", default=None, help="ground-truth pictures (default: DIR/gt)")
+    ap.add_argument("--sample_dir", default=None, help="generated pictures (default: DIR/samples)")
+    ap.add_argument("--gpu", type=int, default=0, help="device ordinal")
+    ap.add_argument("--batch_size", type=int, default=100, help="pictures per kernel call")
+    a = ap.parse_args(argv)
+    if a.dir is None and not (a.gt_dir and a.sample_dir):
+        ap.error("give --dir, or both --gt_dir and --sample_dir")
+    res = run_metrics(a.dir, a.gt_dir, a.sample_dir, a.batch_size, a.gpu if torch.cuda.is_available() else None)
+    for k in ("SSIM", "MSSIM"):
+        print("%s: %r" % (k, res[k]))
+    print("%d pictures, %d skipped" % (res["n"], len(res["skipped"])))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -1,0 +1,105 @@
+"""SSIM and MS-SSIM of uint8 picture pairs on the device: what scripts/eval_metrics.py:110-111 gets from
+pytorch_msssim.ssim / ms_ssim (data_range=1, size_average=False), per image.
+
+The pixel work (11-tap Gaussian moments, the two rational maps, their per-channel means, the 2 x 2 pooling pyramid) is
+upk_ssim_u8 (include/upk.h, csrc/metrics.hip): 2 * levels launches per batch, whatever its size.  What is left acts on
+6 * levels numbers per image and is written here: the relu, the level weights, the product and the channel mean.
+The algorithm is stated in include/upk.h and DESIGN.md 17.
+"""
+import torch
+
+from . import _lib
+from ._check import require
+
+MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+WINDOW = 11          # taps of the Gaussian window: the smallest side a level may have
+MS_MIN_SIDE = 160    # ms_ssim needs min(H, W) > 160 = (WINDOW - 1) * 2^4
+
+_WS = {}  # (device index, lane, H, W, levels) -> uint8 workspace tensor, large enough for the largest batch seen
+
+
+def level_sizes(h, w, levels):
+    """[(h, w)] of every level: avg_pool2d(2, 2, padding = size % 2) takes s to (s + 1) // 2."""
+    out = []
+    for _ in range(levels):
+        out.append((h, w))
+        h, w = (h + 1) // 2, (w + 1) // 2
+    return out
+
+
+def _workspace(ctx, n, h, w, levels):
+    """The workspace of a shape, kept per (device, lane, H, W, levels) as the plans are and grown when a larger batch
+    comes: one entry per picture size, whatever batch sizes (a directory's tail batches) are seen.  A replaced tensor
+    goes back to the caching allocator, which keeps it for the launches already queued on the lane's stream."""
+    key = (ctx.device.index, _lib.current_lane(), h, w, levels)
+    nbytes = ctx.ssim_ws_bytes(n, h, w, levels)
+    require(nbytes > 0, "upk_ssim_ws_bytes refused (%d, %d, %d, %d)" % (n, h, w, levels), RuntimeError)
+    with _lib.PLAN_LOCK:
+        ws = _WS.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = _WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=ctx.device)
+    return ws
+
+
+def _check_pictures(name, a, b):
+    require(torch.is_tensor(a) and torch.is_tensor(b) and a.is_cuda and b.is_cuda,
+            "%s needs device tensors: there is no CPU fallback for the HIP path" % name, RuntimeError)
+    require(a.dtype == torch.uint8 and b.dtype == torch.uint8, "%s: pictures must be uint8" % name, TypeError)
+    require(a.dim() == 4 and a.shape[3] == 3 and a.shape == b.shape,
+            "%s: pictures must be two [N, H, W, 3] tensors of one shape, got %s and %s" % (name, tuple(a.shape), tuple(b.shape)),
+            ValueError)
+    require(a.device == b.device, "%s: both pictures must be on one device" % name, ValueError)
+    n, h, w = a.shape[0], a.shape[1], a.shape[2]
+    require(n >= 1, "%s: empty batch" % name, ValueError)
+    for t in (a, b):
+        require(t.stride(3) == 1 and t.stride(2) == 3, "%s: pixels must be dense inside a row" % name, ValueError)
+        require(t.stride(1) >= 3 * w, "%s: row pitch %d below 3 * W" % (name, t.stride(1)), ValueError)
+        require(n == 1 or t.stride(0) >= (h - 1) * t.stride(1) + 3 * w, "%s: samples overlap (sample stride %d)" % (
+            name, t.stride(0)), ValueError)
+    return n, h, w
+
+
+def ssim_levels(a, b, levels):
+    """[N, levels, 3, 2] fp32 on the pictures' device: (ssim_c, cs_c), the means of the SSIM map and of the
+    contrast-structure map per level and channel.  a, b: uint8 device tensors [N, H, W, 3], pixels dense inside a row, any
+    row pitch / sample stride (a window of a strip is compared in place).  One upk_ssim_u8 call on the current stream;
+    no synchronisation.  Host tensors raise: no CPU fallback."""
+    n, h, w = _check_pictures("ssim_levels", a, b)
+    levels = int(levels)
+    require(1 <= levels <= len(MS_WEIGHTS), "ssim_levels: levels must be 1 .. %d, got %d" % (len(MS_WEIGHTS), levels), ValueError)
+    hl, wl = level_sizes(h, w, levels)[-1]
+    require(min(hl, wl) >= WINDOW, "ssim_levels: level %d of a %d x %d picture is %d x %d, smaller than the %d-tap window" % (
+        levels - 1, h, w, hl, wl, WINDOW), ValueError)
+    ctx = _lib.get_context(a.device)
+    ws = _workspace(ctx, n, h, w, levels)
+    out = torch.empty((n, levels, 3, 2), dtype=torch.float32, device=a.device)
+    ctx.ssim_u8(a, a.stride(1), a.stride(0), b, b.stride(1), b.stride(0), n, h, w, levels, out, ws, ws.numel())
+    return out
+
+
+def ssim_from_levels(lv):
+    """[N] fp64: the channel mean of ssim_c at level 0 (no relu)."""
+    return lv[:, 0, :, 0].double().mean(1)
+
+
+def ms_ssim_from_levels(lv):
+    """[N] fp64 of a 5-level result: per channel prod_{l<4} relu(cs_c[l])^w[l] * relu(ssim_c[4])^w[4], then the channel
+    mean."""
+    require(lv.shape[1] == len(MS_WEIGHTS), "ms_ssim needs %d levels, got %d" % (len(MS_WEIGHTS), lv.shape[1]), ValueError)
+    lv = lv.double()
+    vals = torch.cat([lv[:, :-1, :, 1], lv[:, -1:, :, 0]], 1).clamp_min(0)  # [N, 5, 3]
+    wt = torch.tensor(MS_WEIGHTS, dtype=torch.float64, device=lv.device).view(1, -1, 1)
+    return (vals ** wt).prod(1).mean(1)
+
+
+def ssim(a, b):
+    """[N] fp32 device tensor: pytorch_msssim.ssim(X, Y, data_range=1, size_average=False) of the pictures / 255."""
+    return ssim_from_levels(ssim_levels(a, b, 1)).float()
+
+
+def ms_ssim(a, b):
+    """[N] fp32 device tensor: pytorch_msssim.ms_ssim(X, Y, data_range=1, size_average=False) of the pictures / 255."""
+    _check_pictures("ms_ssim", a, b)
+    require(min(a.shape[1], a.shape[2]) > MS_MIN_SIDE, "ms_ssim: the smaller side must be larger than %d, got %d x %d" % (
+        MS_MIN_SIDE, a.shape[1], a.shape[2]), ValueError)
+    return ms_ssim_from_levels(ssim_levels(a, b, len(MS_WEIGHTS))).float()
