@@ -619,6 +619,65 @@ int upk_ssim_u8(upk_ctx* ctx, const uint8_t* a, long long a_pitch, long long a_s
                 size_t ws_bytes, upk_stream stream);
 
 /* ------------------------------------------------------------------ */
+/* LPIPS (VGG16) of picture pairs (evaluation metrics).                   */
+/* ------------------------------------------------------------------ */
+/* scripts/eval_metrics.py:112, lpips.LPIPS(net='vgg')(sample, gt) (lpips 0.1.4, version '0.1', lpips=True, spatial=False,
+ * eval mode), for inputs in0, in1 [N, 3, H, W]:
+ *   scaling    x' = (x - shift[c]) / scale[c], shift = (-.030, -.088, -.188), scale = (.458, .448, .450); with normalize
+ *              x is 2 x - 1 first.  eval_metrics.py passes T.ToTensor() output, u / 255, with normalize=False.
+ *   features   torchvision VGG16 `features`: 13 convolutions 3x3, stride 1, pad 1, with bias, each followed by a ReLU, in five
+ *              slices of 2, 2, 3, 3, 3 convolutions (3->64->64 | ->128->128 | ->256->256->256 | ->512->512->512 | 512 x3);
+ *              slices 2..5 start with MaxPool2d(2, 2) (floor: an odd side s becomes (s - 1) / 2, the last row / column is
+ *              dropped).  Tap l = the output of the last ReLU of slice l (relu1_2, relu2_2, relu3_3, relu4_3, relu5_3).
+ *   distance   per tap and pixel f^ = f / (sqrt(sum_c f_c^2) + 1e-10); d_l = mean over pixels of sum_c w_l[c] (f^0_c - f^1_c)^2
+ *              with w_l the 1x1 `lin` weight (no bias; dropout is the identity in eval mode); LPIPS = sum_l d_l.
+ *   min(H, W) >= 16, so that the fifth tap has a pixel.
+ * The convolutions are upk_conv2d_nhwc_f16 launches as they stand (plain epilogue, bias, fp16 NHWC output; relu(fp16(v)) ==
+ * fp16(relu(v)), so a ReLU behind the rounding loses nothing); the three entry points below are what is left.  All of them
+ * never allocate, never synchronise, are graph-capturable, and count their launches in class "other".
+ *
+ * upk_lpips_input_f16: pictures -> y fp16 NHWC [batch, h * w, 32]: channels 0..2 = ((x [* 2 - 1]) - shift[c]) / scale[c],
+ * channels 3..31 zero (the first convolution reads 32-channel chunks).
+ *   src_f32 == 0  src is uint8 HWC: byte (c) of pixel (y, x) of sample n at src[n * sample_stride + y * pitch + 3 x + c]
+ *                 (strides in bytes: a window of a strip is read in place), x = u / 255
+ *   src_f32 != 0  src is fp32 NCHW, every sample dense, sample_stride floats apart (pitch is ignored)
+ *   shift_scale_host: HOST array {shift[0..2], scale[0..2]}, read before the call returns.
+ * Every operation is ONE correctly rounded IEEE fp32 operation in the order written (u / 255; 2 * x, then - 1; - shift;
+ * / scale; no FMA contraction), and the result is rounded once to fp16: bit for bit what torch's fp32 expression
+ * followed by .half() gives.  sample_stride and y_sample_stride are ignored for batch == 1.
+ * Errors: UPK_EINVAL for null pointers, non-positive sizes, y not 16-byte / fp32 src not 4-byte aligned, pitch < 3 w,
+ * overlapping samples or outputs, a zero or non-finite scale / non-finite shift; UPK_ESHAPE for more than 2^31 - 1 workgroups. */
+int upk_lpips_input_f16(upk_ctx* ctx, const void* src, int src_f32, long long pitch, long long sample_stride, int batch,
+                        int h, int w, int normalize, const float* shift_scale_host, void* y, long long y_sample_stride,
+                        upk_stream stream);
+/* x [batch, h * w, ld] fp16 (c valid channels per row) becomes relu(x) IN PLACE; with pooled != NULL also pooled[batch,
+ * (h / 2) * (w / 2), ld_p] = the 2x2 stride-2 floor max-pool of the ReLU'd values (an odd last row / column gets its ReLU
+ * and takes no part in the pooling).  16-byte accesses, every input element is read once; channels >= c of a row (the
+ * gap of ld > c) are neither read nor written.  Bit-exact by construction (relu(v) = v > 0 ? v : +0).
+ * Errors: UPK_EINVAL for null x, non-positive sizes, ld / ld_p below c or not a multiple of 8, pointers not 16-byte
+ * aligned; UPK_ESHAPE for c % 8 != 0, pooled with h < 2 or w < 2, more than 2^31 - 1 workgroups. */
+int upk_relu_pool_nhwc_f16(upk_ctx* ctx, void* x, int ld, int batch, int h, int w, int c, void* pooled, int ld_p,
+                           upk_stream stream);
+/* One tap: out[i * 5 + layer] = d_layer of pair i (see above) for i < n, from f0, f1 [n, hw, ld] fp16, the post-ReLU
+ * features of the two pictures, pair i at f0 + i * batch_stride and f1 + i * batch_stride elements (>= hw * ld, a multiple of
+ * 8; ignored for n == 1: one buffer that holds the pictures interleaved is f1 = f0 + hw * ld with batch_stride = 2 hw ld,
+ * two halves of one 2 n batch are f1 = f0 + n * hw * ld with batch_stride = hw ld), c channels, and w [c] fp32.
+ * fp32 arithmetic, eps = 1e-10, IEEE divisions and square root (no approximate reciprocals); an all-zero pixel adds
+ * exactly 0.  c in {64, 128, 256, 512}: a wave covers 512 channels with one 16-byte load per lane (512 / c pixels side by
+ * side), every feature element is read once, the channel sums are shuffles inside the wave.
+ * Deterministic like upk_ssim_u8: no float atomics; every workgroup (16384 / c pixels of one pair) writes its own slot
+ * of ws and a fixed-order fp64 pass sums a pair's slots and divides by hw: reruns are bit-identical, and a pair's value
+ * depends neither on its position in the batch nor on the batch size.  Every term is non-negative, so the result is
+ * within relative (c * hw + 16) * 2^-23 of the exact value for the given fp16 features.
+ *   ws   upk_lpips_ws_bytes(n, hw, c) bytes (0 for arguments upk_lpips_layer_f16 would refuse), 16-byte aligned
+ * Errors: UPK_EINVAL for null pointers, non-positive sizes, layer outside 0..4, ld below c or not a multiple of 8, a batch stride
+ * below hw * ld or not a multiple of 8, f0 / f1 / w / ws not 16-byte or out not 4-byte aligned; UPK_ESHAPE for another c or too many workgroups;
+ * UPK_EWORKSPACE for ws_bytes below upk_lpips_ws_bytes.  Two launches (partial sums, final pass). */
+size_t upk_lpips_ws_bytes(int n, int hw, int c);
+int upk_lpips_layer_f16(upk_ctx* ctx, const void* f0, const void* f1, int ld, long long batch_stride, int n, int hw, int c,
+                        const float* w, int layer, float* out, void* ws, size_t ws_bytes, upk_stream stream);
+
+/* ------------------------------------------------------------------ */
 /* CU-partitioned streams (execution lanes on disjoint CU sets).         */
 /* The reference has no counterpart: it runs one batch on `cuda:0`       */
 /* (app.py:21); lanes are this build's serving mode. */

@@ -28,6 +28,7 @@ SYMBOLS = [
     "upk_ddim_step_cfg_f32", "upk_ddim_step_edit_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
     "upk_patchify_nchw_f32_f16", "upk_vit_assemble_f16", "upk_gather_rows_f16",
     "upk_image_finish_u8", "upk_ssim_ws_bytes", "upk_ssim_u8",
+    "upk_lpips_input_f16", "upk_relu_pool_nhwc_f16", "upk_lpips_ws_bytes", "upk_lpips_layer_f16",
     "upk_advance_step", "upk_step_autoadvance", "upk_kernel_launches", "upk_graph_begin", "upk_graph_end", "upk_graph_launch", "upk_graph_destroy",
     "upk_prof_enable", "upk_prof_collect",
     "upk_stream_create_cumask", "upk_stream_destroy", "upk_probe_placement", "upk_probe_clock",
@@ -186,6 +187,10 @@ def load_library(path=None):
                                               C.POINTER(C.c_float), vp]),
             "upk_ssim_ws_bytes": (C.c_size_t, [i32, i32, i32, i32]),
             "upk_ssim_u8": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, vp, vp, C.c_size_t, vp]),
+            "upk_lpips_input_f16": (C.c_int, [vp, vp, i32, i64, i64, i32, i32, i32, i32, C.POINTER(C.c_float), vp, i64, vp]),
+            "upk_relu_pool_nhwc_f16": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp]),
+            "upk_lpips_ws_bytes": (C.c_size_t, [i32, i32, i32]),
+            "upk_lpips_layer_f16": (C.c_int, [vp, vp, vp, i32, i64, i32, i32, i32, vp, i32, vp, vp, C.c_size_t, vp]),
             "upk_advance_step": (C.c_int, [vp, vp, vp]),
             "upk_step_autoadvance": (C.c_int, [vp, vp]),
             "upk_kernel_launches": (C.c_longlong, [vp, i32]),
@@ -366,6 +371,25 @@ class Context:
         self._chk(self.lib.upk_ssim_u8(self.h, _ptr(a), int(a_pitch), int(a_ss), _ptr(b), int(b_pitch), int(b_ss),
                                        int(batch), int(h), int(w), int(levels), _ptr(out), _ptr(ws), int(ws_bytes),
                                        self._s()))
+
+    def lpips_input(self, src, src_f32, pitch, sample_stride, batch, h, w, normalize, shift_scale, y, y_stride):
+        """upk_lpips_input_f16; shift_scale: the six host floats {shift[0..2], scale[0..2]}."""
+        ss = (C.c_float * 6)(*[float(v) for v in shift_scale])
+        self._chk(self.lib.upk_lpips_input_f16(self.h, _ptr(src), int(bool(src_f32)), int(pitch), int(sample_stride),
+                                               int(batch), int(h), int(w), int(bool(normalize)), ss, _ptr(y), int(y_stride), self._s()))
+
+    def relu_pool(self, x, ld, batch, h, w, c, pooled=None, ld_p=0):
+        """upk_relu_pool_nhwc_f16: ReLU in place; pooled (may be None) <- the 2x2 floor max-pool of the result."""
+        self._chk(self.lib.upk_relu_pool_nhwc_f16(self.h, _ptr(x), int(ld), int(batch), int(h), int(w), int(c),
+                                                  _ptr(pooled), int(ld_p), self._s()))
+
+    def lpips_ws_bytes(self, n, hw, c):
+        return self.lib.upk_lpips_ws_bytes(int(n), int(hw), int(c))
+
+    def lpips_layer(self, f0, f1, ld, batch_stride, n, hw, c, w, layer, out, ws, ws_bytes):
+        """upk_lpips_layer_f16: out[i * 5 + layer] = d_layer of pair i."""
+        self._chk(self.lib.upk_lpips_layer_f16(self.h, _ptr(f0), _ptr(f1), int(ld), int(batch_stride), int(n), int(hw), int(c), _ptr(w),
+                                               int(layer), _ptr(out), _ptr(ws), int(ws_bytes), self._s()))
 
     def step_autoadvance(self, done):
         """Arms (done: zeroed device int32) or disarms (None) the step kernels' own increment of *step."""

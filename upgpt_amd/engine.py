@@ -28,8 +28,8 @@ from . import knobs as K
 from ._check import require
 from .arch import UNetArch, VAEArch
 from .emitter import Act, Emitter, Program  # noqa: F401  (re-exported: scripts and tests import them from here)
-from .packing import (PW, PackedUNet, PackedVAEDecoder, PackedVAEEncoder, Packer, _rup, geglu_rows_map,  # noqa: F401
-                      head_pad, pad_rows_map, qproj_pack)
+from .packing import (PW, PackedUNet, PackedVAEDecoder, PackedVAEEncoder, PackedVGG16, Packer, _rup,  # noqa: F401
+                      geglu_rows_map, head_pad, pad_rows_map, qproj_pack, vgg16_convs)
 from .tuning import TUNE_CACHE, TuneCache  # noqa: F401
 
 
@@ -376,6 +376,73 @@ class VAEEncodePlan(Emitter):
         self.x.copy_(img)
         self.prog.run()
         return self.moments
+
+
+class LpipsPlan(Emitter):
+    """lpips.LPIPS(net='vgg') (include/upk.h) for `pairs` picture pairs of H x W: scaling layer -> 13 x (conv
+    3x3 + ReLU, a max-pool in front of slices 2..5) -> the five tap distances, out [pairs, 5] fp32.
+
+    The 2 * pairs pictures live in ONE NHWC batch, the two pictures of a pair next to each other (2 i, 2 i + 1): the input
+    pass, the 13 ReLU (+ pool) passes and the five tap kernels each cover the whole batch in one call.  The convolutions are
+    upk_conv2d_nhwc_f16 as it stands with the cost model's tile / split-K choice, launched PER PAIR (batch 2): that choice
+    depends on the launch's row count, and different tiles or split-K factors round differently, so a launch over the whole
+    batch would make a pair's value depend on how many pairs share its pass.  Per pair the launch shape is a function of
+    (H, W) alone, and so are the bits of the result."""
+
+    def __init__(self, ctx, packed: PackedVGG16, pairs, H, W):
+        super().__init__(ctx)
+        require(pairs >= 1 and min(H, W) >= 16, "LPIPS needs min(H, W) >= 16 (the fifth tap must have a pixel), got %d x %d" % (H, W),
+                ValueError)
+        self.pk, self.pairs, self.H, self.W = packed, pairs, H, W
+        B = 2 * pairs
+        self.xin = Act(self.alloc(B * H * W, 32), B, H, W, 3)
+        self.out = self.alloc(pairs, 5, dtype=torch.float32)
+        self.ws = self.alloc(max(16, max(ctx.lpips_ws_bytes(pairs, (H >> l) * (W >> l), c)
+                                         for l, c in enumerate((64, 128, 256, 512, 512)))), dtype=torch.uint8)
+        self.prog = P = Program(ctx)
+        self.n_relu = 0
+        convs = vgg16_convs()
+        x = self.xin
+        for j, (s, i, cin, cout) in enumerate(convs):
+            pw = packed.w["net.slice%d.%d" % (s, i)]
+            y = Act(self.alloc(x.M, cout), x.B, x.H, x.W, cout)
+            hw = x.H * x.W
+            for k in range(pairs):  # (per pair: see the class docstring)
+                rows = slice(2 * k * hw, 2 * (k + 1) * hw)
+                self.conv(P, Act(x.t[rows], 2, x.H, x.W, x.C), pw, out=Act(y.t[rows], 2, x.H, x.W, cout))
+            tap = j + 1 == len(convs) or convs[j + 1][0] != s
+            pooled = None
+            if tap and j + 1 < len(convs):
+                pooled = Act(self.alloc(x.B * (x.H // 2) * (x.W // 2), cout), x.B, x.H // 2, x.W // 2, cout)
+            self._relu(P, y, pooled)
+            if tap:
+                self._layer(P, y, s - 1)
+            x = pooled if pooled is not None else y
+
+    def _relu(self, P, y, pooled):
+        fn, h, chk = self.lib.upk_relu_pool_nhwc_f16, self.hctx, self._chk
+        a = (y.t.data_ptr(), y.ld, y.B, y.H, y.W, y.C, pooled.t.data_ptr() if pooled is not None else None,
+             pooled.ld if pooled is not None else 0)
+        P.add(lambda s: chk(fn(h, *a, s)), y, pooled, cls="other", label="relu%s M%d C%d" % ("+pool" if pooled is not None else "", y.M, y.C))
+        self.n_relu += 1
+
+    def _layer(self, P, y, l):
+        fn, h, chk = self.lib.upk_lpips_layer_f16, self.hctx, self._chk
+        hw, w = y.H * y.W, self.pk.lin[l]
+        a = (y.t.data_ptr(), y.t[hw:].data_ptr(), y.ld, 2 * hw * y.ld, self.pairs, hw, y.C, w.data_ptr(), l,
+             self.out.data_ptr(), self.ws.data_ptr(), self.ws.numel())
+        P.add(lambda s: chk(fn(h, *a, s)), y, w, cls="other", label="lpips tap %d hw%d C%d" % (l, hw, y.C))
+        P.n_launch += 1  # partial sums + final pass
+
+    def run(self, src0, src1, f32, normalize):
+        """src0, src1: the two sides of the pairs, (tensor, row pitch, sample stride) as upk_lpips_input_f16 takes them.
+        Returns the plan's own [pairs, 5] buffer (overwritten by the next run)."""
+        hw32 = self.H * self.W * 32
+        for side, (t, pitch, ss) in enumerate((src0, src1)):
+            self.ctx.lpips_input(t, f32, pitch, ss, self.pairs, self.H, self.W, normalize, self.pk.shift_scale,
+                                 self.xin.t[side * self.H * self.W:], 2 * hw32)
+        self.prog.run()
+        return self.out
 
 
 # ====================================================================== sampler step graph

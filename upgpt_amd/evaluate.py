@@ -8,8 +8,8 @@ arithmetic contract (one correctly rounded fp32 operation at a time, in the refe
 where the reference's .byte() is undefined) is stated in include/upk.h and DESIGN.md 16.
 
 run_metrics is the step after it (scripts/eval_metrics.py): results/gt against results/samples -> metrics.csv and
-metrics.txt with per-image SSIM and MS-SSIM from upk_ssim_u8 (upgpt_amd/metrics.py, DESIGN.md 17);
-`python -m upgpt_amd.evaluate --dir <save_dir>/results` runs it.
+metrics.txt with per-image SSIM and MS-SSIM from upk_ssim_u8 (upgpt_amd/metrics.py) and, given the two
+public weight files, LPIPS (upgpt_amd/lpips.py); `python -m upgpt_amd.evaluate --dir <save_dir>/results` runs it.
 """
 import os
 from pathlib import Path
@@ -196,9 +196,33 @@ def _decode(path):
         return None
 
 
-def run_metrics(results_dir=None, gt_dir=None, sample_dir=None, batch_size=100, device=None):
-    """scripts/eval_metrics.py's SSIM and MS-SSIM columns (its lines 110-111) for a results tree.  LPIPS and FID are not
-    computed.
+def _lpips_net(lpips, device):
+    """run_metrics' `lpips` argument -> an LPIPS on `device`, or None: an instance, a (vgg16_path, lin_path) pair, or the
+    environment variables UPGPT_LPIPS_VGG / UPGPT_LPIPS_LIN (both, or neither)."""
+    from .lpips import LPIPS
+    if lpips is None:
+        vgg, lin = os.environ.get("UPGPT_LPIPS_VGG"), os.environ.get("UPGPT_LPIPS_LIN")
+        if not vgg and not lin:
+            return None
+        require(vgg and lin, "UPGPT_LPIPS_VGG and UPGPT_LPIPS_LIN must both be set (torchvision's vgg16 state dict and "
+                "lpips' weights/v0.1/vgg.pth)", ValueError)
+        lpips = (vgg, lin)
+    if isinstance(lpips, LPIPS):
+        return lpips
+    require(isinstance(lpips, (tuple, list)) and len(lpips) == 2, "lpips must be an LPIPS instance or a (vgg16_path, "
+            "lin_path) pair", TypeError)
+    return LPIPS.from_files(lpips[0], lpips[1]).to(device)
+
+
+def run_metrics(results_dir=None, gt_dir=None, sample_dir=None, batch_size=100, device=None, lpips=None):
+    """scripts/eval_metrics.py's SSIM and MS-SSIM columns (its lines 110-111) for a results tree, and its LPIPS column
+    (line 112) when the weights are given.  FID is not computed; LPIPS needs the user's two weight files.
+
+    lpips: an upgpt_amd.lpips.LPIPS instance or a (vgg16_path, lin_path) pair (torchvision's vgg16 state dict and lpips'
+    weights/v0.1/vgg.pth); None reads the pair from UPGPT_LPIPS_VGG / UPGPT_LPIPS_LIN.  With weights metrics.csv has the
+    columns name, SSIM, LPIPS, MSSIM (the reference's order), metrics.txt a third line LPIPS: <mean>, the result the key
+    "LPIPS", and every batch one more device -> host copy (5 floats per picture); LPIPS is NaN for a picture with a side
+    below 16 and its mean ignores those.  Without weights every output is what it was before LPIPS existed.
 
     gt_dir / sample_dir default to results_dir/gt and results_dir/samples.  Every *.jpg / *.png of sample_dir is paired
     with the file of the same name in gt_dir, decoded by PIL, grouped by picture size and sent to the device in batches of
@@ -224,6 +248,7 @@ def run_metrics(results_dir=None, gt_dir=None, sample_dir=None, batch_size=100, 
         device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
     device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
     nl = len(metrics.MS_WEIGHTS)
+    net = _lpips_net(lpips, device)
     rows, skipped, pending = {}, [], {}
 
     def flush(size):
@@ -235,7 +260,11 @@ def run_metrics(results_dir=None, gt_dir=None, sample_dir=None, batch_size=100, 
             lv = metrics.ssim_levels(a, b, nl if deep else 1).cpu()  # the one device -> host copy of the batch
         s = metrics.ssim_from_levels(lv).tolist()
         m = metrics.ms_ssim_from_levels(lv).tolist() if deep else [float("nan")] * len(names)
-        rows.update({n: (si, mi) for n, si, mi in zip(names, s, m)})
+        lp = [float("nan")] * len(names)
+        if net is not None and min(size) >= metrics.LPIPS_MIN_SIDE:
+            with torch.no_grad():
+                lp = metrics.lpips_from_layers(metrics.lpips_layers(a, b, net).cpu()).tolist()  # (the batch's second copy)
+        rows.update({n: (si, mi, li) for n, si, mi, li in zip(names, s, m, lp)})
 
     for name in sorted(f.name for f in sample_dir.iterdir() if f.suffix in (".jpg", ".png") and f.is_file()):
         smp = _decode(sample_dir / name)
@@ -257,32 +286,43 @@ def run_metrics(results_dir=None, gt_dir=None, sample_dir=None, batch_size=100, 
     ms_ok = ms_vals[~np.isnan(ms_vals)]
     means = {"SSIM": float(ssim_vals.mean()) if len(names) else float("nan"),
              "MSSIM": float(ms_ok.mean()) if ms_ok.size else float("nan")}
+    if net is not None:
+        lp_vals = np.array([rows[n][2] for n in names], dtype=np.float64)
+        lp_ok = lp_vals[~np.isnan(lp_vals)]
+        means["LPIPS"] = float(lp_ok.mean()) if lp_ok.size else float("nan")
     log_dir = sample_dir.resolve().parent
     with open(str(log_dir / "metrics.csv"), "w", newline="") as f:
         wr = csv.writer(f)
-        wr.writerow(["name", "SSIM", "MSSIM"])
+        wr.writerow(["name", "SSIM"] + (["LPIPS"] if net is not None else []) + ["MSSIM"])
         for n in names:
-            wr.writerow([n, repr(rows[n][0]), repr(rows[n][1])])
+            wr.writerow([n, repr(rows[n][0])] + ([repr(rows[n][2])] if net is not None else []) + [repr(rows[n][1])])
     with open(str(log_dir / "metrics.txt"), "w") as f:
-        for k in ("SSIM", "MSSIM"):
+        for k in ("SSIM", "MSSIM") + (("LPIPS",) if net is not None else ()):
             f.write("%s: %r\n" % (k, means[k]))
     return dict(means, n=len(names), skipped=skipped)
 
 
 def main(argv=None):
     import argparse
-    ap = argparse.ArgumentParser(prog="python -m upgpt_amd.evaluate", description="SSIM / MS-SSIM of a results tree "
-                                 "(gt against samples) -> metrics.csv, metrics.txt next to the samples folder")
+    ap = argparse.ArgumentParser(prog="python -m upgpt_amd.evaluate", description="SSIM / MS-SSIM (and, with the two weight "
+                                 "files, LPIPS) of a results tree (gt against samples) -> metrics.csv, metrics.txt next to "
+                                 "the samples folder")
     ap.add_argument("--dir", default=None, help="results directory holding gt/ and samples/")
     ap.add_argument("--gt_dir", default=None, help="ground-truth pictures (default: DIR/gt)")
     ap.add_argument("--sample_dir", default=None, help="generated pictures (default: DIR/samples)")
     ap.add_argument("--gpu", type=int, default=0, help="device ordinal")
     ap.add_argument("--batch_size", type=int, default=100, help="pictures per kernel call")
+    ap.add_argument("--lpips_vgg", default=None, help="torchvision's vgg16 state dict (default: $UPGPT_LPIPS_VGG); with "
+                    "--lpips_lin it adds the LPIPS column")
+    ap.add_argument("--lpips_lin", default=None, help="lpips' weights/v0.1/vgg.pth (default: $UPGPT_LPIPS_LIN)")
     a = ap.parse_args(argv)
     if a.dir is None and not (a.gt_dir and a.sample_dir):
         ap.error("give --dir, or both --gt_dir and --sample_dir")
-    res = run_metrics(a.dir, a.gt_dir, a.sample_dir, a.batch_size, a.gpu if torch.cuda.is_available() else None)
-    for k in ("SSIM", "MSSIM"):
+    if bool(a.lpips_vgg) != bool(a.lpips_lin):
+        ap.error("give both --lpips_vgg and --lpips_lin, or neither")
+    res = run_metrics(a.dir, a.gt_dir, a.sample_dir, a.batch_size, a.gpu if torch.cuda.is_available() else None,
+                      lpips=(a.lpips_vgg, a.lpips_lin) if a.lpips_vgg else None)
+    for k in ("SSIM", "MSSIM") + (("LPIPS",) if "LPIPS" in res else ()):
         print("%s: %r" % (k, res[k]))
     print("%d pictures, %d skipped" % (res["n"], len(res["skipped"])))
     return 0

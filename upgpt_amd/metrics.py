@@ -5,6 +5,9 @@ The pixel work (11-tap Gaussian moments, the two rational maps, their per-channe
 upk_ssim_u8 (include/upk.h, csrc/metrics.hip): 2 * levels launches per batch, whatever its size.  What is left acts on
 6 * levels numbers per image and is written here: the relu, the level weights, the product and the channel mean.
 The algorithm is stated in include/upk.h and DESIGN.md 17.
+
+lpips / lpips_layers: the LPIPS (VGG16) column of the same script (its line 112) through an upgpt_amd.lpips.LPIPS
+instance that holds the user's weights.
 """
 import torch
 
@@ -14,6 +17,7 @@ from ._check import require
 MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 WINDOW = 11          # taps of the Gaussian window: the smallest side a level may have
 MS_MIN_SIDE = 160    # ms_ssim needs min(H, W) > 160 = (WINDOW - 1) * 2^4
+LPIPS_MIN_SIDE = 16  # lpips needs min(H, W) >= 16: the fifth VGG tap must have a pixel
 
 _WS = {}  # (device index, lane, H, W, levels) -> uint8 workspace tensor, large enough for the largest batch seen
 
@@ -103,3 +107,23 @@ def ms_ssim(a, b):
     require(min(a.shape[1], a.shape[2]) > MS_MIN_SIDE, "ms_ssim: the smaller side must be larger than %d, got %d x %d" % (
         MS_MIN_SIDE, a.shape[1], a.shape[2]), ValueError)
     return ms_ssim_from_levels(ssim_levels(a, b, len(MS_WEIGHTS))).float()
+
+
+def lpips_layers(a, b, net):
+    """[N, 5] fp32 on the pictures' device: the five tap distances d_l of lpips.LPIPS(net='vgg')(a / 255, b / 255), what
+    scripts/eval_metrics.py:112 computes (ToTensor output, normalize=False).  a, b as for ssim_levels; net: an
+    upgpt_amd.lpips.LPIPS on the same device.  Host tensors raise: no CPU fallback."""
+    from .lpips import LPIPS
+    require(isinstance(net, LPIPS), "lpips needs an upgpt_amd.lpips.LPIPS instance (the weights are the user's)", TypeError)
+    _check_pictures("lpips", a, b)
+    return net.pairs_u8(a, b)
+
+
+def lpips_from_layers(lv):
+    """[N] fp64: the sum of the five tap values."""
+    return lv.double().sum(1)
+
+
+def lpips(a, b, net):
+    """[N] fp32 device tensor: lpips.LPIPS(net='vgg')(a / 255, b / 255) per pair (summed in fp64, rounded once)."""
+    return lpips_from_layers(lpips_layers(a, b, net)).float()

@@ -366,3 +366,38 @@ class PackedVAEEncoder:
         self.w, self.v = w, v
 
 
+# ====================================================================== VGG16 features (LPIPS)
+# torchvision's vgg16().features indices of the 13 convolutions, by LPIPS slice; slices 2..5 start with a max-pool
+VGG16_SLICES = ((0, 2), (5, 7), (10, 12, 14), (17, 19, 21), (24, 26, 28))
+VGG16_TAP_CHANNELS = (64, 128, 256, 512, 512)
+
+
+def vgg16_convs():
+    """[(slice 1..5, features index, cin, cout)] of the 13 convolutions in order."""
+    out, cin = [], 3
+    for s, (idxs, cout) in enumerate(zip(VGG16_SLICES, VGG16_TAP_CHANNELS), 1):
+        for i in idxs:
+            out.append((s, i, cin, cout))
+            cin = cout
+    return out
+
+
+class PackedVGG16:
+    """The 13 convolutions of lpips' `net` (keys net.slice<s>.<i>.{weight,bias}) packed for upk_conv2d_nhwc_f16 (conv1_1
+    has its 3 input channels padded to 32), the five `lin` weights as fp32 vectors and the scaling layer's six numbers
+    on the host."""
+
+    def __init__(self, ctx, get):
+        pk = Packer(ctx, get)
+        self.w, self.lin = {}, []
+        for s, i, cin, cout in vgg16_convs():
+            name = "net.slice%d.%d" % (s, i)
+            self.w[name] = pk.pack(name, cin_packed=_rup(cin, 32))
+        for l, c in enumerate(VGG16_TAP_CHANNELS):
+            v = pk.vec("lin%d.model.1.weight" % l).reshape(-1)
+            require(v.numel() == c, "lin%d has %d weights, the tap has %d channels" % (l, v.numel(), c), ValueError)
+            self.lin.append(v.contiguous())
+        shift = get("scaling_layer.shift").detach().float().reshape(-1).cpu().tolist()
+        scale = get("scaling_layer.scale").detach().float().reshape(-1).cpu().tolist()
+        require(len(shift) == 3 and len(scale) == 3, "scaling_layer.shift / scale must hold three numbers each", ValueError)
+        self.shift_scale = tuple(shift) + tuple(scale)

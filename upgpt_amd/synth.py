@@ -75,6 +75,26 @@ def fill_ema_(module, salt=1):
     return new
 
 
+def synthetic_lpips_state(seed=0):
+    """An lpips-style state dict (upgpt_amd/lpips.py: its keys, lpips' shapes) by recipe; the real weights are the
+    user's.  Conv weights are He-normal (std = sqrt(2 / (9 cin)): a ReLU network keeps its activation scale through the
+    13 layers, well inside fp16's range), biases small normal, `lin` weights non-negative (uniform[0, 1) / C_l; lpips'
+    own are non-negative too), shift / scale the constants of lpips' ScalingLayer."""
+    from .lpips import SCALE, SHIFT, param_shapes
+    sd = {}
+    for k, shape in param_shapes().items():
+        g = _gen("lpips." + k, seed)
+        if k.startswith("lin"):
+            sd[k] = torch.rand(shape, generator=g, dtype=torch.float32) / shape[1]
+        elif k.endswith(".weight"):
+            sd[k] = torch.randn(shape, generator=g, dtype=torch.float32) * math.sqrt(2.0 / (9 * shape[1]))
+        else:
+            sd[k] = 0.05 * torch.randn(shape, generator=g, dtype=torch.float32)
+    sd["scaling_layer.shift"] = torch.tensor(SHIFT, dtype=torch.float32).view(1, 3, 1, 1)
+    sd["scaling_layer.scale"] = torch.tensor(SCALE, dtype=torch.float32).view(1, 3, 1, 1)
+    return sd
+
+
 def crc_of(t):
     return zlib.crc32(t.detach().cpu().contiguous().numpy().tobytes()) & 0xFFFFFFFF
 
