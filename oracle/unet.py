@@ -81,16 +81,24 @@ def unet_layout(cfg):
     return inputs, middle, outputs
 
 
+_ROUND = None  # unet_forward(round_fn=...): applied to every layer output (a storage-precision model of the activations)
+
+
+def _r(t):
+    return t if _ROUND is None else _ROUND(t)
+
+
 def _gn(sd, name, x, eps):
-    return F.group_norm(x.float(), 32, sd[name + ".weight"], sd[name + ".bias"], eps).type(x.dtype)
+    w = sd[name + ".weight"]  # (statistics in the precision of the weights: fp32 as the reference, fp64 when asked)
+    return _r(F.group_norm(x.to(w.dtype), 32, w, sd[name + ".bias"], eps).type(x.dtype))
 
 
 def _conv(sd, name, x, stride=1, padding=1):
-    return F.conv2d(x, sd[name + ".weight"], sd[name + ".bias"], stride=stride, padding=padding)
+    return _r(F.conv2d(x, sd[name + ".weight"], sd[name + ".bias"], stride=stride, padding=padding))
 
 
 def _lin(sd, name, x):
-    return F.linear(x, sd[name + ".weight"], sd.get(name + ".bias"))
+    return _r(F.linear(x, sd[name + ".weight"], sd.get(name + ".bias")))
 
 
 def resblock(sd, p, x, emb):
@@ -98,11 +106,11 @@ def resblock(sd, p, x, emb):
     + Linear(SiLU(emb)) broadcast, GN+SiLU+conv3x3, + skip (identity | conv1x1)."""
     h = _conv(sd, p + ".in_layers.2", F.silu(_gn(sd, p + ".in_layers.0", x, 1e-5)))
     e = _lin(sd, p + ".emb_layers.1", F.silu(emb))
-    h = h + e[:, :, None, None]
+    h = _r(h + e[:, :, None, None])
     h = _conv(sd, p + ".out_layers.3", F.silu(_gn(sd, p + ".out_layers.0", h, 1e-5)))
     if (p + ".skip_connection.weight") in sd:
         x = _conv(sd, p + ".skip_connection", x, padding=0)
-    return x + h
+    return _r(x + h)
 
 
 def cross_attention(sd, p, x, context, heads):
@@ -115,19 +123,19 @@ def cross_attention(sd, p, x, context, heads):
     split = lambda t: t.reshape(b, t.shape[1], heads, d).permute(0, 2, 1, 3).reshape(b * heads, t.shape[1], d)
     q, k, v = split(q), split(k), split(v)
     sim = torch.einsum("bid,bjd->bij", q, k) * (d ** -0.5)
-    out = torch.einsum("bij,bjd->bid", sim.softmax(dim=-1), v)
+    out = _r(torch.einsum("bij,bjd->bid", sim.softmax(dim=-1), v))
     out = out.reshape(b, heads, n, d).permute(0, 2, 1, 3).reshape(b, n, inner)
     return _lin(sd, p + ".to_out.0", out)
 
 
 def transformer_block(sd, p, x, context, heads):
     """attention.py:211-215 + GEGLU feed-forward 42-44, 63-64 (LayerNorm eps 1e-5)."""
-    ln = lambda nm, t: F.layer_norm(t, (t.shape[-1],), sd[p + nm + ".weight"], sd[p + nm + ".bias"], 1e-5)
-    x = cross_attention(sd, p + ".attn1", ln(".norm1", x), None, heads) + x
-    x = cross_attention(sd, p + ".attn2", ln(".norm2", x), context, heads) + x
+    ln = lambda nm, t: _r(F.layer_norm(t, (t.shape[-1],), sd[p + nm + ".weight"], sd[p + nm + ".bias"], 1e-5))
+    x = _r(cross_attention(sd, p + ".attn1", ln(".norm1", x), None, heads) + x)
+    x = _r(cross_attention(sd, p + ".attn2", ln(".norm2", x), context, heads) + x)
     hcat = _lin(sd, p + ".ff.net.0.proj", ln(".norm3", x))
     val, gate = hcat.chunk(2, dim=-1)
-    return _lin(sd, p + ".ff.net.2", val * F.gelu(gate)) + x
+    return _r(_lin(sd, p + ".ff.net.2", _r(val * F.gelu(gate))) + x)
 
 
 def spatial_transformer(sd, p, x, context, heads, depth=1):
@@ -138,7 +146,7 @@ def spatial_transformer(sd, p, x, context, heads, depth=1):
     for d in range(depth):
         t = transformer_block(sd, p + ".transformer_blocks.%d" % d, t, context, heads)
     t = t.reshape(b, h, w, -1).permute(0, 3, 1, 2)
-    return _conv(sd, p + ".proj_out", t, padding=0) + x
+    return _r(_conv(sd, p + ".proj_out", t, padding=0) + x)
 
 
 def _run_layers(sd, prefix, layers, h, emb, context, depth):
@@ -158,14 +166,27 @@ def _run_layers(sd, prefix, layers, h, emb, context, depth):
 
 
 @torch.no_grad()
-def unet_forward(sd, cfg, x, timesteps, context, prefix="model.diffusion_model.", taps=None):
-    """openaimodel.py:710-742. `taps` (dict) receives per-block outputs for debugging."""
+def unet_forward(sd, cfg, x, timesteps, context, prefix="model.diffusion_model.", taps=None, dtype=torch.float32,
+                 round_fn=None):
+    """openaimodel.py:710-742. `taps` (dict) receives per-block outputs for debugging.  dtype: precision of the whole
+    evaluation (the caller passes `sd` and `context` in it; fp32 is the reference's).  round_fn: applied to every layer
+    output (conv, Linear, norm, attention, GEGLU product, residual sum), e.g. a round trip through fp16, to model
+    activations stored at a lower precision than they are computed in."""
+    global _ROUND
+    prev, _ROUND = _ROUND, round_fn
+    try:
+        return _unet_forward(sd, cfg, x, timesteps, context, prefix, taps, dtype)
+    finally:
+        _ROUND = prev
+
+
+def _unet_forward(sd, cfg, x, timesteps, context, prefix, taps, dtype):
     inputs, middle, outputs = unet_layout(cfg)
     depth = cfg.get("transformer_depth", 1)
-    temb = timestep_embedding(timesteps, cfg["model_channels"])
+    temb = timestep_embedding(timesteps, cfg["model_channels"]).to(dtype)
     emb = _lin(sd, prefix + "time_embed.2", F.silu(_lin(sd, prefix + "time_embed.0", temb)))
     hs = []
-    h = x.float()
+    h = x.to(dtype)
     for i, layers in enumerate(inputs):
         h = _run_layers(sd, prefix, layers, h, emb, context, depth)
         hs.append(h)
