@@ -678,6 +678,87 @@ int upk_lpips_layer_f16(upk_ctx* ctx, const void* f0, const void* f1, int ld, lo
                         const float* w, int layer, float* out, void* ws, size_t ws_bytes, upk_stream stream);
 
 /* ------------------------------------------------------------------ */
+/* FID features: InceptionV3 of pytorch_fid (evaluation metrics).         */
+/* ------------------------------------------------------------------ */
+/* scripts/eval_metrics.py:102, `python -m pytorch_fid gt_dir sample_dir` (pytorch_fid 0.3.0, dims = 2048): the [N, 2048]
+ * pool3 features of its InceptionV3 (pt_inception-2015-12-05 weights, eval mode) for pictures x [N, 3, H, W] in [0, 1]:
+ *   input      F.interpolate(x, size = (299, 299), mode = 'bilinear', align_corners = False), no antialias also when
+ *              shrinking: source coordinate s = max(0, (d + 0.5) * in / 299 - 0.5), i0 = floor(s), i1 = min(i0 + 1, in - 1),
+ *              weight lambda = s - i0, per axis; then 2 x - 1.
+ *   conv unit  BasicConv2d = Conv2d(bias = False) -> BatchNorm2d(eps = 1e-3, eval) -> ReLU.  The BatchNorm is folded when the
+ *              weights are packed (fp64, rounded once): w' = w g / sqrt(var + 1e-3) (fp16), b' = beta - mean g / sqrt(var +
+ *              1e-3) (fp32).  All paddings 0 unless given; "avg" is avg_pool2d(3, stride 1, pad 1, count_include_pad = False):
+ *              the divisor is the number of taps inside the picture.
+ *   trunk      Conv2d_1a_3x3 3 -> 32 3x3 s2 (149) | Conv2d_2a_3x3 32 -> 32 3x3 (147) | Conv2d_2b_3x3 32 -> 64 3x3 p1 (147) |
+ *              max pool 3x3 s2 (73) | Conv2d_3b_1x1 64 -> 80 1x1 | Conv2d_4a_3x3 80 -> 192 3x3 (71) | max pool 3x3 s2 (35) |
+ *              Mixed_5b, 5c, 5d = A(192, 32), A(256, 64), A(288, 64) -> 256, 288, 288 (35) | Mixed_6a = B(288) -> 768 (17) |
+ *              Mixed_6b .. 6e = C(768, c7 = 128, 160, 160, 192) -> 768 | Mixed_7a = D(768) -> 1280 (8) | Mixed_7b = E(1280,
+ *              avg), Mixed_7c = E(2048, MAX) -> 2048 | mean over the pixels -> [N, 2048]
+ *   blocks     (branches concatenated along C in this order)
+ *     A(in, pf)  branch1x1 in -> 64 | branch5x5_1 in -> 48 1x1, branch5x5_2 48 -> 64 5x5 p2 | branch3x3dbl_1 in -> 64 1x1, _2
+ *                64 -> 96 3x3 p1, _3 96 -> 96 3x3 p1 | avg, branch_pool in -> pf 1x1
+ *     B(288)     branch3x3 288 -> 384 3x3 s2 | branch3x3dbl_1 288 -> 64 1x1, _2 64 -> 96 3x3 p1, _3 96 -> 96 3x3 s2 | max pool
+ *                3x3 s2 of the input
+ *     C(768, c7) branch1x1 -> 192 | branch7x7_1 -> c7 1x1, _2 c7 -> c7 (1,7) p(0,3), _3 c7 -> 192 (7,1) p(3,0) | branch7x7dbl_1
+ *                -> c7 1x1, _2 (7,1) p(3,0), _3 (1,7) p(0,3), _4 (7,1) p(3,0) all c7 -> c7, _5 (1,7) p(0,3) c7 -> 192 | avg,
+ *                branch_pool -> 192 1x1
+ *     D(768)     branch3x3_1 -> 192 1x1, branch3x3_2 192 -> 320 3x3 s2 | branch7x7x3_1 -> 192 1x1, _2 (1,7) p(0,3), _3 (7,1)
+ *                p(3,0), _4 3x3 s2, all 192 -> 192 | max pool 3x3 s2 of the input
+ *     E(in)      branch1x1 -> 320 | branch3x3_1 -> 384 1x1, then branch3x3_2a (1,3) p(0,1) and branch3x3_2b (3,1) p(1,0), both
+ *                384 -> 384 reading _1, concatenated | branch3x3dbl_1 -> 448 1x1, _2 448 -> 384 3x3 p1, then _3a (1,3) p(0,1)
+ *                and _3b (3,1) p(1,0) both reading _2, concatenated | pool, branch_pool -> 192 1x1; the pool is avg in
+ *                Mixed_7b and max_pool2d(3, stride 1, pad 1) in Mixed_7c
+ * All four entry points never allocate, never synchronise and are graph-capturable.  The convolution counts in class
+ * "igemm", the three others in class "other".
+ *
+ * upk_conv2d_rect_f16: y[m, 0 .. n_out) = act(conv(x, w)[m] + bias) for the batch * ho * wo output pixels m of an NHWC fp16
+ * input x [batch, in_h * in_w, ldx] (cin_pad valid channels, a multiple of 32, zero-padded), ho = (in_h + 2 pad_h - kh) /
+ * stride + 1 and wo likewise; kh, kw in 1 .. 7 independently, stride 1 or 2 (both axes), pad_h, pad_w in 0 .. 3 (zeros).
+ *   w_packed  upk_pack_weight_f16 layout [kh * kw * cin_pad / 32][n_pad][32]
+ *   bias      fp32 [n_pad] in packed row order, or NULL; relu != 0: max(v, +0) before the fp16 rounding
+ *   y, ldy    row m at y + m * ldy, ldy >= n_out: a branch writes its channel slice of a concatenated output in place;
+ *             columns >= n_out of a row are never touched
+ * MFMA implicit GEMM, fp32 accumulation.  The tile (128 pixels x 64 channels, 32 for n_pad < 64) depends on n_pad alone and
+ * K is never split: an output element is one accumulation chain over k = (ky, kx, ci) in ascending order, so its bits do
+ * not depend on the batch size or on the picture's place in the batch, and reruns are bit-identical (no atomics).
+ * Errors: UPK_ESHAPE for kh / kw / stride / paddings outside the above, cin_pad not a positive multiple of 32, n_pad not a
+ * multiple of 16, n_out outside 1 .. n_pad, more than 2^31 - 1 pixels; UPK_EINVAL for null x / w_packed / y, non-positive sizes,
+ * ldy < n_out, ldx < cin_pad, ldx % 8, ldy % 4, x / w_packed / bias not 16-byte or y not 8-byte aligned, an output extent that
+ * is not positive (in + 2 pad < k). */
+int upk_conv2d_rect_f16(upk_ctx* ctx, const void* x, int ldx, int batch, int in_h, int in_w, int cin_pad, int kh, int kw,
+                        int stride, int pad_h, int pad_w, const void* w_packed, int n_out, int n_pad, const float* bias,
+                        int relu, void* y, int ldy, upk_stream stream);
+/* 3x3 pooling of x [batch, h * w, ldx] fp16 (c valid channels, a multiple of 8) into y [batch, ho * wo, ldy]: stride 1 with
+ * padding 1 (ho = h, wo = w) or stride 2 without padding (ho = (h - 3) / 2 + 1).  Taps outside the picture take no part:
+ * UPK_POOL_MAX is the maximum of the in-picture taps (bit-exact), UPK_POOL_AVG their fp32 sum in (ky, kx) order divided
+ * once (IEEE) by their NUMBER (count_include_pad = False), rounded once to fp16.  Channels >= c of a row are neither read
+ * nor written.
+ * Errors: UPK_EINVAL for null pointers, non-positive sizes, another mode, ldx / ldy below c or not a multiple of 8, pointers
+ * not 16-byte aligned; UPK_ESHAPE for another stride, c % 8 != 0, stride 2 with h < 3 or w < 3, too many workgroups. */
+#define UPK_POOL_MAX 0
+#define UPK_POOL_AVG 1
+int upk_pool3_nhwc_f16(upk_ctx* ctx, const void* x, int ldx, int batch, int h, int w, int c, int mode, int stride, void* y,
+                       int ldy, upk_stream stream);
+/* pictures -> y fp16 NHWC [batch, out_h * out_w, 32]: the bilinear resize above from h x w to out_h x out_w (equal sizes:
+ * a copy, lambda = 0), then 2 x - 1 when normalize != 0; channels 3 .. 31 are +0.  Sources as upk_lpips_input_f16 takes them:
+ *   src_f32 == 0  uint8 HWC, byte (c) of pixel (y, x) of sample n at src[n * sample_stride + y * pitch + 3 x + c], x = u / 255
+ *   src_f32 != 0  fp32 NCHW, every sample dense, sample_stride floats apart (pitch is ignored)
+ * Sample n is written at y + n * y_sample_stride elements (>= 32 out_h out_w, a multiple of 8).  The source coordinate and
+ * lambda are formed in fp64 and lambda rounded once; the pixel arithmetic is fp32, one IEEE operation at a time, no FMA: v = u /
+ * 255; t = (1 - lx) v00 + lx v01 for both rows; (1 - ly) t0 + ly t1; 2 x, - 1; one rounding to fp16.  sample_stride and
+ * y_sample_stride are ignored for batch == 1.
+ * Errors: UPK_EINVAL for null pointers, non-positive sizes (a zero output size included), y not 16-byte / fp32 src not 4-byte
+ * aligned, pitch < 3 w, overlapping samples or outputs; UPK_ESHAPE for more than 2^31 - 1 workgroups. */
+int upk_fid_input_f16(upk_ctx* ctx, const void* src, int src_f32, long long pitch, long long sample_stride, int batch, int h,
+                      int w, int out_h, int out_w, int normalize, void* y, long long y_sample_stride, upk_stream stream);
+/* out[i, ch] = the mean over the hw pixels of x [n, hw, ld] fp16 (c valid channels, a multiple of 8; sample i at x + i * hw *
+ * ld), fp32 [n, c] dense: an fp32 sum in pixel order, one IEEE division; reruns are bit-identical and a sample's value does not
+ * depend on the batch.  Within (hw + 2) 2^-24 mean|x| of the exact mean.
+ * Errors: UPK_EINVAL for null pointers, non-positive sizes, ld below c or not a multiple of 8, x not 16-byte or out not
+ * 4-byte aligned; UPK_ESHAPE for c % 8 != 0, too many workgroups. */
+int upk_avgpool_global_f32(upk_ctx* ctx, const void* x, int ld, int n, int hw, int c, float* out, upk_stream stream);
+
+/* ------------------------------------------------------------------ */
 /* CU-partitioned streams (execution lanes on disjoint CU sets).         */
 /* The reference has no counterpart: it runs one batch on `cuda:0`       */
 /* (app.py:21); lanes are this build's serving mode. */

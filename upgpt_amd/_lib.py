@@ -29,6 +29,7 @@ SYMBOLS = [
     "upk_patchify_nchw_f32_f16", "upk_vit_assemble_f16", "upk_gather_rows_f16",
     "upk_image_finish_u8", "upk_ssim_ws_bytes", "upk_ssim_u8",
     "upk_lpips_input_f16", "upk_relu_pool_nhwc_f16", "upk_lpips_ws_bytes", "upk_lpips_layer_f16",
+    "upk_conv2d_rect_f16", "upk_pool3_nhwc_f16", "upk_fid_input_f16", "upk_avgpool_global_f32",
     "upk_advance_step", "upk_step_autoadvance", "upk_kernel_launches", "upk_graph_begin", "upk_graph_end", "upk_graph_launch", "upk_graph_destroy",
     "upk_prof_enable", "upk_prof_collect",
     "upk_stream_create_cumask", "upk_stream_destroy", "upk_probe_placement", "upk_probe_clock",
@@ -39,6 +40,7 @@ DDPM_X0, DDPM_CLIP = 0x1, 0x2  # upk_ddpm_step_f32 flags
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1  # upk_image_finish_u8 source layouts
 FINISH_SAMPLE, FINISH_INPUT, FINISH_DENORM = 0, 1, 2  # ... and arithmetic modes
 F_QUICKGELU = 0x40
+POOL_MAX, POOL_AVG = 0, 1  # upk_pool3_nhwc_f16 modes
 NUM_CLASSES = 5
 CLASS_NAMES = ["igemm", "attention", "groupnorm", "layernorm", "other"]
 
@@ -191,6 +193,11 @@ def load_library(path=None):
             "upk_relu_pool_nhwc_f16": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp]),
             "upk_lpips_ws_bytes": (C.c_size_t, [i32, i32, i32]),
             "upk_lpips_layer_f16": (C.c_int, [vp, vp, vp, i32, i64, i32, i32, i32, vp, i32, vp, vp, C.c_size_t, vp]),
+            "upk_conv2d_rect_f16": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, vp,
+                                              i32, vp]),
+            "upk_pool3_nhwc_f16": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
+            "upk_fid_input_f16": (C.c_int, [vp, vp, i32, i64, i64, i32, i32, i32, i32, i32, i32, vp, i64, vp]),
+            "upk_avgpool_global_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, vp]),
             "upk_advance_step": (C.c_int, [vp, vp, vp]),
             "upk_step_autoadvance": (C.c_int, [vp, vp]),
             "upk_kernel_launches": (C.c_longlong, [vp, i32]),
@@ -390,6 +397,27 @@ class Context:
         """upk_lpips_layer_f16: out[i * 5 + layer] = d_layer of pair i."""
         self._chk(self.lib.upk_lpips_layer_f16(self.h, _ptr(f0), _ptr(f1), int(ld), int(batch_stride), int(n), int(hw), int(c), _ptr(w),
                                                int(layer), _ptr(out), _ptr(ws), int(ws_bytes), self._s()))
+
+    def conv2d_rect(self, x, ldx, batch, h, w, cin_pad, kh, kw, stride, pad_h, pad_w, w_packed, n_out, n_pad, bias, relu, y, ldy):
+        """upk_conv2d_rect_f16: y[m, :n_out] = act(conv(x, w)[m] + bias), rows ldy apart (a channel slice of a wider buffer)."""
+        self._chk(self.lib.upk_conv2d_rect_f16(self.h, _ptr(x), int(ldx), int(batch), int(h), int(w), int(cin_pad), int(kh), int(kw),
+                                               int(stride), int(pad_h), int(pad_w), _ptr(w_packed), int(n_out), int(n_pad),
+                                               _ptr(bias), int(bool(relu)), _ptr(y), int(ldy), self._s()))
+
+    def pool3(self, x, ldx, batch, h, w, c, mode, stride, y, ldy):
+        """upk_pool3_nhwc_f16: mode POOL_MAX / POOL_AVG (in-picture divisor); stride 1 (pad 1) or 2 (pad 0)."""
+        self._chk(self.lib.upk_pool3_nhwc_f16(self.h, _ptr(x), int(ldx), int(batch), int(h), int(w), int(c), int(mode), int(stride),
+                                              _ptr(y), int(ldy), self._s()))
+
+    def fid_input(self, src, src_f32, pitch, sample_stride, batch, h, w, out_h, out_w, normalize, y, y_stride):
+        """upk_fid_input_f16: bilinear resize to out_h x out_w, 2 x - 1 (normalize), fp16 NHWC with 32 channels."""
+        self._chk(self.lib.upk_fid_input_f16(self.h, _ptr(src), int(bool(src_f32)), int(pitch), int(sample_stride), int(batch),
+                                             int(h), int(w), int(out_h), int(out_w), int(bool(normalize)), _ptr(y), int(y_stride),
+                                             self._s()))
+
+    def avgpool_global(self, x, ld, n, hw, c, out):
+        """upk_avgpool_global_f32: fp16 [n, hw, ld] -> fp32 [n, c] means."""
+        self._chk(self.lib.upk_avgpool_global_f32(self.h, _ptr(x), int(ld), int(n), int(hw), int(c), _ptr(out), self._s()))
 
     def step_autoadvance(self, done):
         """Arms (done: zeroed device int32) or disarms (None) the step kernels' own increment of *step."""

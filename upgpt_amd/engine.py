@@ -445,6 +445,159 @@ class LpipsPlan(Emitter):
         return self.out
 
 
+class _Map:
+    """A [B * H * W, C] window of an fp16 activation buffer: channels off .. off + C of rows `ld` apart."""
+    __slots__ = ("t", "off", "B", "H", "W", "C")
+
+    def __init__(self, t, off, B, H, W, C):
+        self.t, self.off, self.B, self.H, self.W, self.C = t, off, B, H, W, C
+
+    @property
+    def ld(self):
+        return self.t.shape[1]
+
+    @property
+    def ptr(self):
+        return self.t.data_ptr() + 2 * self.off
+
+
+class FidPlan(Emitter):
+    """pytorch_fid's InceptionV3 (include/upk.h) for `pictures` pictures of H x W: upk_fid_input_f16 (bilinear
+    resize to 299 x 299 when `resize`) -> 94 upk_conv2d_rect_f16 launches, 4 + 9 upk_pool3_nhwc_f16 launches (every branch
+    writes its channel slice of the block's output: no concat pass) -> upk_avgpool_global_f32, out [pictures, 2048] fp32.
+
+    All pictures share every launch: the convolution's tile and K walk do not depend on the batch (include/upk.h), so a
+    picture's bits do not either.  Buffers of a finished block are handed to the next one (the launches are in stream order)."""
+
+    def __init__(self, ctx, packed, pictures, H, W, resize):
+        super().__init__(ctx)
+        from .packing import FID_DIMS, INCEPTION_A, INCEPTION_C, INCEPTION_E, inception_units
+        self.pk, self.B, self.H, self.W, self.resize = packed, pictures, H, W, bool(resize)
+        self.units = inception_units()
+        self.in_h, self.in_w = (299, 299) if resize else (H, W)
+        require(pictures >= 1 and min(self.in_h, self.in_w) >= 75, "InceptionV3 without resizing needs min(H, W) >= 75 (Mixed_7a "
+                "must leave a pixel), got %d x %d" % (H, W), ValueError)
+        self._free, self._live = {}, []
+        self.prog = P = Program(ctx)
+        self.xin = self._new(self.in_h, self.in_w, 3)
+        self.out = self.alloc(pictures, FID_DIMS, dtype=torch.float32)
+        MAX, AVG = L.POOL_MAX, L.POOL_AVG
+        conv, pool, new, sl, give = self._conv, self._pool, self._new, self._slice, self._give
+        x = self.xin
+        for name in ("Conv2d_1a_3x3", "Conv2d_2a_3x3", "Conv2d_2b_3x3"):
+            x = conv(P, x, name)
+        x = pool(P, x, MAX, 2)
+        x = conv(P, conv(P, x, "Conv2d_3b_1x1"), "Conv2d_4a_3x3")
+        x = pool(P, x, MAX, 2)
+        for n, cin, pf in INCEPTION_A:
+            y = new(x.H, x.W, 224 + pf)
+            conv(P, x, n + ".branch1x1", sl(y, 0, 64))
+            conv(P, conv(P, x, n + ".branch5x5_1"), n + ".branch5x5_2", sl(y, 64, 64))
+            conv(P, conv(P, conv(P, x, n + ".branch3x3dbl_1"), n + ".branch3x3dbl_2"), n + ".branch3x3dbl_3", sl(y, 128, 96))
+            conv(P, pool(P, x, AVG, 1), n + ".branch_pool", sl(y, 224, pf))
+            x = give(y)
+        n = "Mixed_6a"
+        y = new((x.H - 3) // 2 + 1, (x.W - 3) // 2 + 1, 768)
+        conv(P, x, n + ".branch3x3", sl(y, 0, 384))
+        conv(P, conv(P, conv(P, x, n + ".branch3x3dbl_1"), n + ".branch3x3dbl_2"), n + ".branch3x3dbl_3", sl(y, 384, 96))
+        pool(P, x, MAX, 2, sl(y, 480, 288))
+        x = give(y)
+        for n, c7 in INCEPTION_C:
+            y = new(x.H, x.W, 768)
+            conv(P, x, n + ".branch1x1", sl(y, 0, 192))
+            t = conv(P, conv(P, x, n + ".branch7x7_1"), n + ".branch7x7_2")
+            conv(P, t, n + ".branch7x7_3", sl(y, 192, 192))
+            t = conv(P, x, n + ".branch7x7dbl_1")
+            for k in (2, 3, 4):
+                t = conv(P, t, n + ".branch7x7dbl_%d" % k)
+            conv(P, t, n + ".branch7x7dbl_5", sl(y, 384, 192))
+            conv(P, pool(P, x, AVG, 1), n + ".branch_pool", sl(y, 576, 192))
+            x = give(y)
+        n = "Mixed_7a"
+        y = new((x.H - 3) // 2 + 1, (x.W - 3) // 2 + 1, 1280)
+        conv(P, conv(P, x, n + ".branch3x3_1"), n + ".branch3x3_2", sl(y, 0, 320))
+        t = conv(P, x, n + ".branch7x7x3_1")
+        for k in (2, 3):
+            t = conv(P, t, n + ".branch7x7x3_%d" % k)
+        conv(P, t, n + ".branch7x7x3_4", sl(y, 320, 192))
+        pool(P, x, MAX, 2, sl(y, 512, 768))
+        x = give(y)
+        for n, cin, kind in INCEPTION_E:
+            y = new(x.H, x.W, 2048)
+            conv(P, x, n + ".branch1x1", sl(y, 0, 320))
+            t = conv(P, x, n + ".branch3x3_1")
+            conv(P, t, n + ".branch3x3_2a", sl(y, 320, 384))
+            conv(P, t, n + ".branch3x3_2b", sl(y, 704, 384))
+            t = conv(P, conv(P, x, n + ".branch3x3dbl_1"), n + ".branch3x3dbl_2")
+            conv(P, t, n + ".branch3x3dbl_3a", sl(y, 1088, 384))
+            conv(P, t, n + ".branch3x3dbl_3b", sl(y, 1472, 384))
+            conv(P, pool(P, x, AVG if kind == "avg" else MAX, 1), n + ".branch_pool", sl(y, 1856, 192))
+            x = give(y)
+        fn, h, chk = self.lib.upk_avgpool_global_f32, self.hctx, self._chk
+        a = (x.ptr, x.ld, x.B, x.H * x.W, x.C, self.out.data_ptr())
+        P.add(lambda s: chk(fn(h, *a, s)), x.t, self.out, cls="other", label="global mean hw%d C%d" % (x.H * x.W, x.C))
+        self.last = x
+
+    # ---- buffers: a block's temporaries and its input go back to the pool when the block is emitted
+    def _new(self, H, W, C):
+        rows, ld = self.B * H * W, _rup(C, 32)
+        require(rows * ld < 2 ** 31, "FidPlan: a %d x %d map of %d pictures and %d channels passes 2^31 elements; lower "
+                "pictures_per_pass" % (H, W, self.B, C), ValueError)
+        lst = self._free.get((rows, ld))
+        t = lst.pop() if lst else self.alloc(rows, ld)
+        self._live.append(t)
+        return _Map(t, 0, self.B, H, W, C)
+
+    def _give(self, keep):
+        """End of a block: every buffer taken since the last call except `keep`'s is free again (the block's input and its
+        temporaries are dead once its launches are in the stream; whoever takes them next writes behind those launches)."""
+        for t in self._live:
+            if t is not keep.t:
+                self._free.setdefault(tuple(t.shape), []).append(t)
+        self._live = [keep.t]
+        return keep
+
+    @staticmethod
+    def _slice(y, off, c):
+        return _Map(y.t, y.off + off, y.B, y.H, y.W, c)
+
+    def _conv(self, P, x, name, dst=None):
+        cin, cout, kh, kw, s, ph, pw_ = self.units[name]
+        pw = self.pk.u[name]
+        Ho, Wo = (x.H + 2 * ph - kh) // s + 1, (x.W + 2 * pw_ - kw) // s + 1
+        require(x.off == 0 and x.C == cin and pw.k_packed <= x.ld, "%s reads %d channels, its source has %d" % (name, cin, x.C), ValueError)
+        if dst is None:
+            dst = self._new(Ho, Wo, cout)
+        require((dst.H, dst.W) == (Ho, Wo) and dst.C == cout and dst.off + pw.n_out <= dst.ld, "%s: destination %dx%dx%d does not "
+                "take its %dx%dx%d output" % (name, dst.H, dst.W, dst.C, Ho, Wo, cout), ValueError)
+        fn, h, chk = self.lib.upk_conv2d_rect_f16, self.hctx, self._chk
+        a = (x.ptr, x.ld, x.B, x.H, x.W, pw.k_packed, kh, kw, s, ph, pw_, pw.w.data_ptr(), pw.n_out, pw.n_pad, pw.bias.data_ptr(),
+             1, dst.ptr, dst.ld)
+        P.add(lambda st: chk(fn(h, *a, st)), x.t, dst.t, pw, cls="igemm_k%d" % max(kh, kw), label="%s M%d" % (name, x.B * Ho * Wo))
+        fl = 2 * x.B * Ho * Wo * cout * cin * kh * kw
+        P.igemm_flops += fl
+        P.flops[-1] = fl
+        return dst
+
+    def _pool(self, P, x, mode, stride, dst=None):
+        Ho, Wo = (x.H, x.W) if stride == 1 else ((x.H - 3) // 2 + 1, (x.W - 3) // 2 + 1)
+        if dst is None:
+            dst = self._new(Ho, Wo, x.C)
+        fn, h, chk = self.lib.upk_pool3_nhwc_f16, self.hctx, self._chk
+        a = (x.ptr, x.ld, x.B, x.H, x.W, x.C, mode, stride, dst.ptr, dst.ld)
+        P.add(lambda st: chk(fn(h, *a, st)), x.t, dst.t, cls="other", label="pool3 %s s%d M%d C%d" % (
+            "avg" if mode == L.POOL_AVG else "max", stride, x.B * Ho * Wo, x.C))
+        return dst
+
+    def run(self, src, f32, pitch, ss, normalize):
+        """src: the pictures as upk_fid_input_f16 takes them.  Returns the plan's own [pictures, 2048] buffer (overwritten by
+        the next run)."""
+        self.ctx.fid_input(src, f32, pitch, ss, self.B, self.H, self.W, self.in_h, self.in_w, normalize, self.xin.t,
+                           self.in_h * self.in_w * 32)
+        self.prog.run()
+        return self.out
+
+
 # ====================================================================== sampler step graph
 class SamplerState:
     """Device state of one DDIM run on a sampler-mode UNetPlan: latent x (fp32 NCHW),

@@ -9,7 +9,8 @@ where the reference's .byte() is undefined) is stated in include/upk.h and DESIG
 
 run_metrics is the step after it (scripts/eval_metrics.py): results/gt against results/samples -> metrics.csv and
 metrics.txt with per-image SSIM and MS-SSIM from upk_ssim_u8 (upgpt_amd/metrics.py) and, given the two
-public weight files, LPIPS (upgpt_amd/lpips.py); `python -m upgpt_amd.evaluate --dir <save_dir>/results` runs it.
+public weight files, LPIPS (upgpt_amd/lpips.py) and, given pytorch_fid's Inception weights, the FID line of
+metrics.txt (upgpt_amd/fid.py); `python -m upgpt_amd.evaluate --dir <save_dir>/results` runs it.
 """
 import os
 from pathlib import Path
@@ -214,9 +215,68 @@ def _lpips_net(lpips, device):
     return LPIPS.from_files(lpips[0], lpips[1]).to(device)
 
 
-def run_metrics(results_dir=None, gt_dir=None, sample_dir=None, batch_size=100, device=None, lpips=None):
-    """scripts/eval_metrics.py's SSIM and MS-SSIM columns (its lines 110-111) for a results tree, and its LPIPS column
-    (line 112) when the weights are given.  FID is not computed; LPIPS needs the user's two weight files.
+FID_SUFFIXES = frozenset("." + e for e in ("bmp", "jpg", "jpeg", "pgm", "png", "ppm", "tif", "tiff", "webp"))  # pytorch_fid's
+
+
+def _fid_net(fid, device):
+    """run_metrics' `fid` argument -> a FIDInception on `device`, or None: an instance, a path to pytorch_fid's
+    pt_inception-2015-12-05-6726825d.pth, or the environment variable UPGPT_FID_INCEPTION."""
+    from .fid import FIDInception
+    if fid is None:
+        fid = os.environ.get("UPGPT_FID_INCEPTION") or None
+        if fid is None:
+            return None
+    if isinstance(fid, FIDInception):
+        return fid
+    require(isinstance(fid, (str, os.PathLike)), "fid must be a FIDInception instance or the path of the weight file", TypeError)
+    return FIDInception.from_file(fid).to(device)
+
+
+def _fid_of_dirs(net, dirs, batch_size, device):
+    """pytorch_fid's number for two folders: EVERY decodable picture of each (its suffix list, converted to RGB), one size at
+    a time in (height, width, name) order, batches of batch_size through metrics.fid_features (one device -> host copy of
+    2048 floats per picture each), statistics accumulated in fp64 (metrics.FidStats: the order of the pictures, which does
+    not depend on batch_size, fixes every bit)."""
+    from PIL import Image
+
+    from . import metrics
+    stats = []
+    for d in dirs:
+        by_size = {}
+        for f in sorted(p for p in d.iterdir() if p.suffix.lower() in FID_SUFFIXES and p.is_file()):
+            try:
+                with Image.open(str(f)) as im:  # (the header: decoding happens batch by batch below)
+                    by_size.setdefault((im.height, im.width), []).append(f)
+            except Exception:
+                continue
+        acc = metrics.FidStats()
+        for size in sorted(by_size):
+            batch = []
+            for i, f in enumerate(by_size[size]):
+                im = _decode(f)
+                if im is not None and im.shape[:2] == size:
+                    batch.append(im)
+                if batch and (len(batch) >= batch_size or i + 1 == len(by_size[size])):
+                    x = torch.from_numpy(np.stack(batch)).to(device, non_blocking=True)
+                    with torch.no_grad():
+                        acc.add(metrics.fid_features(x, net).cpu())
+                    batch = []
+        stats.append(acc.stats())
+    return metrics.fid_from_stats(*stats[0], *stats[1])
+
+
+def run_metrics(results_dir=None, gt_dir=None, sample_dir=None, batch_size=100, device=None, lpips=None, fid=None):
+    """scripts/eval_metrics.py's SSIM and MS-SSIM columns (its lines 110-111) for a results tree, its LPIPS column
+    (line 112) and its FID line (line 102) when the weights are given: LPIPS needs the user's two weight files, FID
+    pytorch_fid's Inception file.  Without that file FID is not computed.
+
+    fid: an upgpt_amd.fid.FIDInception instance or the path of pt_inception-2015-12-05-6726825d.pth; None reads the path
+    from UPGPT_FID_INCEPTION.  With weights metrics.txt gets, as its FIRST line (where the reference writes pytorch_fid's
+    output), `FID:  <value>` with the two blanks of pytorch_fid's print, and the result the key "FID".  As for pytorch_fid
+    the two sets are EVERY decodable picture of gt_dir and of sample_dir (suffixes bmp, jpg, jpeg, pgm, png, ppm, tif, tiff,
+    webp; converted to RGB), independent of the pairing and of "skipped"; they are grouped by size, taken in (height,
+    width, name) order and batched by batch_size, every batch one more device -> host copy (2048 floats per picture); a
+    set of fewer than two pictures gives NaN.  metrics.csv is not touched by FID, and without weights every output is what it was before FID existed.
 
     lpips: an upgpt_amd.lpips.LPIPS instance or a (vgg16_path, lin_path) pair (torchvision's vgg16 state dict and lpips'
     weights/v0.1/vgg.pth); None reads the pair from UPGPT_LPIPS_VGG / UPGPT_LPIPS_LIN.  With weights metrics.csv has the
@@ -249,6 +309,7 @@ def run_metrics(results_dir=None, gt_dir=None, sample_dir=None, batch_size=100, 
     device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
     nl = len(metrics.MS_WEIGHTS)
     net = _lpips_net(lpips, device)
+    fid_net = _fid_net(fid, device)
     rows, skipped, pending = {}, [], {}
 
     def flush(size):
@@ -290,6 +351,8 @@ def run_metrics(results_dir=None, gt_dir=None, sample_dir=None, batch_size=100, 
         lp_vals = np.array([rows[n][2] for n in names], dtype=np.float64)
         lp_ok = lp_vals[~np.isnan(lp_vals)]
         means["LPIPS"] = float(lp_ok.mean()) if lp_ok.size else float("nan")
+    if fid_net is not None:
+        means["FID"] = _fid_of_dirs(fid_net, (gt_dir, sample_dir), batch_size, device)
     log_dir = sample_dir.resolve().parent
     with open(str(log_dir / "metrics.csv"), "w", newline="") as f:
         wr = csv.writer(f)
@@ -297,6 +360,8 @@ def run_metrics(results_dir=None, gt_dir=None, sample_dir=None, batch_size=100, 
         for n in names:
             wr.writerow([n, repr(rows[n][0])] + ([repr(rows[n][2])] if net is not None else []) + [repr(rows[n][1])])
     with open(str(log_dir / "metrics.txt"), "w") as f:
+        if fid_net is not None:
+            f.write("FID:  %r\n" % means["FID"])  # (pytorch_fid's print('FID: ', value))
         for k in ("SSIM", "MSSIM") + (("LPIPS",) if net is not None else ()):
             f.write("%s: %r\n" % (k, means[k]))
     return dict(means, n=len(names), skipped=skipped)
@@ -304,8 +369,8 @@ def run_metrics(results_dir=None, gt_dir=None, sample_dir=None, batch_size=100, 
 
 def main(argv=None):
     import argparse
-    ap = argparse.ArgumentParser(prog="python -m upgpt_amd.evaluate", description="SSIM / MS-SSIM (and, with the two weight "
-                                 "files, LPIPS) of a results tree (gt against samples) -> metrics.csv, metrics.txt next to "
+    ap = argparse.ArgumentParser(prog="python -m upgpt_amd.evaluate", description="SSIM / MS-SSIM (with the two weight "
+                                 "files LPIPS, with pytorch_fid's Inception weights FID) of a results tree (gt against samples) -> metrics.csv, metrics.txt next to "
                                  "the samples folder")
     ap.add_argument("--dir", default=None, help="results directory holding gt/ and samples/")
     ap.add_argument("--gt_dir", default=None, help="ground-truth pictures (default: DIR/gt)")
@@ -315,13 +380,17 @@ def main(argv=None):
     ap.add_argument("--lpips_vgg", default=None, help="torchvision's vgg16 state dict (default: $UPGPT_LPIPS_VGG); with "
                     "--lpips_lin it adds the LPIPS column")
     ap.add_argument("--lpips_lin", default=None, help="lpips' weights/v0.1/vgg.pth (default: $UPGPT_LPIPS_LIN)")
+    ap.add_argument("--fid_inception", default=None, help="pytorch_fid's pt_inception-2015-12-05-6726825d.pth (default: "
+                    "$UPGPT_FID_INCEPTION); adds the FID line of metrics.txt")
     a = ap.parse_args(argv)
     if a.dir is None and not (a.gt_dir and a.sample_dir):
         ap.error("give --dir, or both --gt_dir and --sample_dir")
     if bool(a.lpips_vgg) != bool(a.lpips_lin):
         ap.error("give both --lpips_vgg and --lpips_lin, or neither")
     res = run_metrics(a.dir, a.gt_dir, a.sample_dir, a.batch_size, a.gpu if torch.cuda.is_available() else None,
-                      lpips=(a.lpips_vgg, a.lpips_lin) if a.lpips_vgg else None)
+                      lpips=(a.lpips_vgg, a.lpips_lin) if a.lpips_vgg else None, fid=a.fid_inception)
+    if "FID" in res:
+        print("FID:  %r" % res["FID"])
     for k in ("SSIM", "MSSIM") + (("LPIPS",) if "LPIPS" in res else ()):
         print("%s: %r" % (k, res[k]))
     print("%d pictures, %d skipped" % (res["n"], len(res["skipped"])))

@@ -8,7 +8,12 @@ The algorithm is stated in include/upk.h and DESIGN.md 17.
 
 lpips / lpips_layers: the LPIPS (VGG16) column of the same script (its line 112) through an upgpt_amd.lpips.LPIPS
 instance that holds the user's weights.
+
+fid_features / FidStats / fid_stats / fid_from_stats: the first line of that script's metrics.txt, pytorch_fid's FID (its line
+102): InceptionV3 features through an upgpt_amd.fid.FIDInception that holds the user's weights, the statistics and the
+Frechet distance on the host in fp64 numpy.
 """
+import numpy as np
 import torch
 
 from . import _lib
@@ -60,6 +65,20 @@ def _check_pictures(name, a, b):
         require(t.stride(1) >= 3 * w, "%s: row pitch %d below 3 * W" % (name, t.stride(1)), ValueError)
         require(n == 1 or t.stride(0) >= (h - 1) * t.stride(1) + 3 * w, "%s: samples overlap (sample stride %d)" % (
             name, t.stride(0)), ValueError)
+    return n, h, w
+
+
+def _check_picture(name, a):
+    """One set of pictures, as _check_pictures checks each side of a pair."""
+    require(torch.is_tensor(a) and a.is_cuda, "%s needs device tensors: there is no CPU fallback for the HIP path" % name, RuntimeError)
+    require(a.dtype == torch.uint8, "%s: pictures must be uint8" % name, TypeError)
+    require(a.dim() == 4 and a.shape[3] == 3, "%s: pictures must be [N, H, W, 3], got %s" % (name, tuple(a.shape)), ValueError)
+    n, h, w = a.shape[0], a.shape[1], a.shape[2]
+    require(n >= 1 and h >= 1 and w >= 1, "%s: empty batch" % name, ValueError)
+    require(a.stride(3) == 1 and a.stride(2) == 3, "%s: pixels must be dense inside a row" % name, ValueError)
+    require(a.stride(1) >= 3 * w, "%s: row pitch %d below 3 * W" % (name, a.stride(1)), ValueError)
+    require(n == 1 or a.stride(0) >= (h - 1) * a.stride(1) + 3 * w, "%s: samples overlap (sample stride %d)" % (name, a.stride(0)),
+            ValueError)
     return n, h, w
 
 
@@ -127,3 +146,83 @@ def lpips_from_layers(lv):
 def lpips(a, b, net):
     """[N] fp32 device tensor: lpips.LPIPS(net='vgg')(a / 255, b / 255) per pair (summed in fp64, rounded once)."""
     return lpips_from_layers(lpips_layers(a, b, net)).float()
+
+
+def fid_features(x, net):
+    """[N, 2048] fp32 on the pictures' device: pytorch_fid's InceptionV3 pool3 features of x / 255 (resized to 299 x 299, 2 x -
+    1).  x: uint8 device tensor [N, H, W, 3] as for ssim_levels; net: an upgpt_amd.fid.FIDInception on the same device.  Host
+    tensors raise: no CPU fallback."""
+    from .fid import FIDInception
+    require(isinstance(net, FIDInception), "fid_features needs an upgpt_amd.fid.FIDInception instance (the weights are the user's)",
+            TypeError)
+    _check_picture("fid_features", x)
+    return net.features_u8(x)
+
+
+class FidStats:
+    """The statistics of a set, accumulated batch by batch in fp64 as the sum and the sum of outer products: no [N, 2048]
+    array of a whole set is kept.  stats() -> (mu, sigma) with sigma = np.cov(rowvar=False) (divisor N - 1); NaN-filled for
+    fewer than two pictures.
+
+    Rows are folded in blocks of exactly CHUNK pictures in arrival order (at most CHUNK - 1 wait in a buffer; stats() folds
+    the tail without consuming it), so the arithmetic, and with it every bit of the result, depends on the ORDER of the
+    pictures only, never on how they were cut into batches.  That matters: for N < D the Frechet distance amplifies a
+    last-bit difference of sigma by many orders of magnitude."""
+    CHUNK = 64
+
+    def __init__(self, dims=2048):
+        self.n, self.s, self.ss = 0, np.zeros(dims, dtype=np.float64), np.zeros((dims, dims), dtype=np.float64)
+        self._pend = np.zeros((0, dims), dtype=np.float64)
+
+    @staticmethod
+    def _fold(n, s, ss, rows):
+        return n + rows.shape[0], s + rows.sum(0), ss + rows.T @ rows
+
+    def add(self, feat):
+        f = np.asarray(feat.detach().cpu() if torch.is_tensor(feat) else feat, dtype=np.float64)
+        require(f.ndim == 2 and f.shape[1] == self.s.shape[0], "FidStats.add: features must be [n, %d], got %s" % (
+            self.s.shape[0], f.shape), ValueError)
+        pend = np.concatenate([self._pend, f], 0)
+        while pend.shape[0] >= self.CHUNK:
+            self.n, self.s, self.ss = self._fold(self.n, self.s, self.ss, np.ascontiguousarray(pend[:self.CHUNK]))
+            pend = pend[self.CHUNK:]
+        self._pend = np.ascontiguousarray(pend)
+        return self
+
+    @property
+    def count(self):
+        return self.n + self._pend.shape[0]
+
+    def stats(self):
+        n, s, ss = self.n, self.s, self.ss
+        if self._pend.shape[0]:
+            n, s, ss = self._fold(n, s, ss, self._pend)
+        if n < 2:
+            return np.full_like(self.s, np.nan), np.full_like(self.ss, np.nan)
+        mu = s / n
+        return mu, (ss - n * np.outer(mu, mu)) / (n - 1)
+
+
+def fid_stats(feat):
+    """(mu, sigma) of features [N, D] (host or device, any float type), fp64 numpy: mu = mean(feat, 0), sigma = np.cov(feat,
+    rowvar=False); NaN-filled for N < 2.  Computed as FidStats computes them, so the batch-wise accumulation of the same
+    rows in the same order gives the same bits."""
+    f = np.asarray(feat.detach().cpu() if torch.is_tensor(feat) else feat, dtype=np.float64)
+    require(f.ndim == 2, "fid_stats: features must be [N, D], got %s" % (f.shape,), ValueError)
+    return FidStats(f.shape[1]).add(f).stats()
+
+
+def fid_from_stats(mu1, sigma1, mu2, sigma2):
+    """|mu1 - mu2|^2 + tr(sigma1) + tr(sigma2) - 2 tr(sqrtm(sigma1 sigma2)), host fp64.  The trace of the principal square
+    root is the sum of the square roots of the eigenvalues of sigma1 sigma2 (np.linalg.eigvals, complex square root, real
+    part kept): the quantity pytorch_fid takes from scipy.linalg.sqrtm, without scipy.  NaN statistics (a set
+    of fewer than two pictures) give NaN."""
+    mu1, mu2 = np.atleast_1d(np.asarray(mu1, dtype=np.float64)), np.atleast_1d(np.asarray(mu2, dtype=np.float64))
+    s1, s2 = np.atleast_2d(np.asarray(sigma1, dtype=np.float64)), np.atleast_2d(np.asarray(sigma2, dtype=np.float64))
+    require(mu1.shape == mu2.shape and s1.shape == s2.shape == (mu1.shape[0], mu1.shape[0]),
+            "fid_from_stats: mean vectors and covariances of different shapes", ValueError)
+    if not (np.isfinite(mu1).all() and np.isfinite(mu2).all() and np.isfinite(s1).all() and np.isfinite(s2).all()):
+        return float("nan")
+    d = mu1 - mu2
+    tr_sqrt = np.sqrt(np.linalg.eigvals(s1 @ s2).astype(np.complex128)).real.sum()
+    return float(d @ d + np.trace(s1) + np.trace(s2) - 2.0 * tr_sqrt)

@@ -401,3 +401,102 @@ class PackedVGG16:
         scale = get("scaling_layer.scale").detach().float().reshape(-1).cpu().tolist()
         require(len(shift) == 3 and len(scale) == 3, "scaling_layer.shift / scale must hold three numbers each", ValueError)
         self.shift_scale = tuple(shift) + tuple(scale)
+
+
+# ====================================================================== InceptionV3 of pytorch_fid (FID)
+BN_EPS = 1e-3  # BasicConv2d's BatchNorm2d
+BN_LEAVES = ("bn.weight", "bn.bias", "bn.running_mean", "bn.running_var")
+INCEPTION_A = (("Mixed_5b", 192, 32), ("Mixed_5c", 256, 64), ("Mixed_5d", 288, 64))
+INCEPTION_C = (("Mixed_6b", 128), ("Mixed_6c", 160), ("Mixed_6d", 160), ("Mixed_6e", 192))
+INCEPTION_E = (("Mixed_7b", 1280, "avg"), ("Mixed_7c", 2048, "max"))
+FID_DIMS = 2048
+
+
+def inception_units():
+    """{unit name: (cin, cout, kh, kw, stride, pad_h, pad_w)} of the 94 BasicConv2d units (include/upk.h), in network order."""
+    u = {}
+
+    def add(name, cin, cout, kh=1, kw=1, s=1, ph=0, pw=0):
+        u[name] = (cin, cout, kh, kw, s, ph, pw)
+
+    add("Conv2d_1a_3x3", 3, 32, 3, 3, 2)
+    add("Conv2d_2a_3x3", 32, 32, 3, 3)
+    add("Conv2d_2b_3x3", 32, 64, 3, 3, 1, 1, 1)
+    add("Conv2d_3b_1x1", 64, 80)
+    add("Conv2d_4a_3x3", 80, 192, 3, 3)
+    for n, cin, pf in INCEPTION_A:
+        add(n + ".branch1x1", cin, 64)
+        add(n + ".branch5x5_1", cin, 48)
+        add(n + ".branch5x5_2", 48, 64, 5, 5, 1, 2, 2)
+        add(n + ".branch3x3dbl_1", cin, 64)
+        add(n + ".branch3x3dbl_2", 64, 96, 3, 3, 1, 1, 1)
+        add(n + ".branch3x3dbl_3", 96, 96, 3, 3, 1, 1, 1)
+        add(n + ".branch_pool", cin, pf)
+    n = "Mixed_6a"
+    add(n + ".branch3x3", 288, 384, 3, 3, 2)
+    add(n + ".branch3x3dbl_1", 288, 64)
+    add(n + ".branch3x3dbl_2", 64, 96, 3, 3, 1, 1, 1)
+    add(n + ".branch3x3dbl_3", 96, 96, 3, 3, 2)
+    for n, c7 in INCEPTION_C:
+        add(n + ".branch1x1", 768, 192)
+        add(n + ".branch7x7_1", 768, c7)
+        add(n + ".branch7x7_2", c7, c7, 1, 7, 1, 0, 3)
+        add(n + ".branch7x7_3", c7, 192, 7, 1, 1, 3, 0)
+        add(n + ".branch7x7dbl_1", 768, c7)
+        add(n + ".branch7x7dbl_2", c7, c7, 7, 1, 1, 3, 0)
+        add(n + ".branch7x7dbl_3", c7, c7, 1, 7, 1, 0, 3)
+        add(n + ".branch7x7dbl_4", c7, c7, 7, 1, 1, 3, 0)
+        add(n + ".branch7x7dbl_5", c7, 192, 1, 7, 1, 0, 3)
+        add(n + ".branch_pool", 768, 192)
+    n = "Mixed_7a"
+    add(n + ".branch3x3_1", 768, 192)
+    add(n + ".branch3x3_2", 192, 320, 3, 3, 2)
+    add(n + ".branch7x7x3_1", 768, 192)
+    add(n + ".branch7x7x3_2", 192, 192, 1, 7, 1, 0, 3)
+    add(n + ".branch7x7x3_3", 192, 192, 7, 1, 1, 3, 0)
+    add(n + ".branch7x7x3_4", 192, 192, 3, 3, 2)
+    for n, cin, _ in INCEPTION_E:
+        add(n + ".branch1x1", cin, 320)
+        add(n + ".branch3x3_1", cin, 384)
+        add(n + ".branch3x3_2a", 384, 384, 1, 3, 1, 0, 1)
+        add(n + ".branch3x3_2b", 384, 384, 3, 1, 1, 1, 0)
+        add(n + ".branch3x3dbl_1", cin, 448)
+        add(n + ".branch3x3dbl_2", 448, 384, 3, 3, 1, 1, 1)
+        add(n + ".branch3x3dbl_3a", 384, 384, 1, 3, 1, 0, 1)
+        add(n + ".branch3x3dbl_3b", 384, 384, 3, 1, 1, 1, 0)
+        add(n + ".branch_pool", cin, 192)
+    return u
+
+
+def fold_batchnorm(w, gamma, beta, mean, var, eps=BN_EPS):
+    """(w', b') of conv -> eval BatchNorm as one conv with bias, in fp64: w' = w g / sqrt(var + eps), b' = beta - mean g /
+    sqrt(var + eps)."""
+    s = gamma.double() / torch.sqrt(var.double() + eps)
+    return w.double() * s.view(-1, 1, 1, 1), beta.double() - mean.double() * s
+
+
+class PackedInception:
+    """The 94 units packed for upk_conv2d_rect_f16: BatchNorm folded in fp64, the weight rounded once to fp16, the bias to
+    fp32.  Output rows are padded to a multiple of 32 with zero rows (a consumer reads 32-channel chunks: the 48- and
+    80-channel outputs carry 16 exact zeros), input channels likewise (3 -> 32, 48 -> 64, 80 -> 96)."""
+
+    def __init__(self, ctx, get):
+        self.u = {}
+        dev = ctx.device
+        for name, (cin, cout, kh, kw, s, ph, pw) in inception_units().items():
+            w, b = fold_batchnorm(get(name + ".conv.weight").detach().cpu(), *[get(name + "." + l).detach().cpu() for l in BN_LEAVES])
+            require(tuple(w.shape) == (cout, cin, kh, kw), "%s.conv.weight has shape %s, expected %s" % (
+                name, tuple(w.shape), (cout, cin, kh, kw)), ValueError)
+            rows = _rup(cout, 32)
+            rm = None
+            if rows != cout:
+                rm = torch.full((rows,), -1, dtype=torch.int32)
+                rm[:cout] = torch.arange(cout, dtype=torch.int32)
+                rm = rm.to(dev)
+            p = PW()
+            p.w, p.n_pad = ctx.pack_weight(w.to(torch.float16).float().contiguous().to(dev), row_map=rm, cin_packed=_rup(cin, 32))
+            p.bias = torch.zeros(p.n_pad, dtype=torch.float32)
+            p.bias[:cout] = b.float()
+            p.bias = p.bias.to(dev)
+            p.n_out, p.n_real, p.k_packed, p.k_real = rows, cout, _rup(cin, 32), cin * kh * kw
+            self.u[name] = p

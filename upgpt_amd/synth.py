@@ -95,6 +95,24 @@ def synthetic_lpips_state(seed=0):
     return sd
 
 
+def synthetic_fid_state(seed=0):
+    """A state dict with pytorch_fid's InceptionV3 keys and shapes (upgpt_amd/fid.py) by recipe; the real weights are the
+    user's.  Convolutions are He-normal (std = sqrt(2 / (kh kw cin))), bn.weight and bn.running_var uniform in [0.5, 1.5],
+    bn.bias and bn.running_mean small normal: the activation scale holds through the 94 units, well inside fp16's range, and
+    most of the 2048 features are alive."""
+    from .fid import param_shapes
+    sd = {}
+    for k, shape in param_shapes().items():
+        g = _gen("fid." + k, seed)
+        if k.endswith("conv.weight"):
+            sd[k] = torch.randn(shape, generator=g, dtype=torch.float32) * math.sqrt(2.0 / (shape[1] * shape[2] * shape[3]))
+        elif k.endswith("bn.weight") or k.endswith("running_var"):
+            sd[k] = 0.5 + torch.rand(shape, generator=g, dtype=torch.float32)
+        else:
+            sd[k] = 0.05 * torch.randn(shape, generator=g, dtype=torch.float32)
+    return sd
+
+
 def crc_of(t):
     return zlib.crc32(t.detach().cpu().contiguous().numpy().tobytes()) & 0xFFFFFFFF
 
