@@ -584,6 +584,49 @@ int upk_image_finish_u8(upk_ctx* ctx, const float* src, int layout, int batch, i
                         const float* denorm_host, upk_stream stream);
 
 /* ------------------------------------------------------------------ */
+/* Low-resolution conditioning: uint8 pictures -> `lr` (upscale stage).   */
+/* ------------------------------------------------------------------ */
+/* What the reference does to a generated picture before the upscale model sees it (app.py:93-97 with p = 4,
+ * deepfashion_inshop.py:427-431 with p = 8): T.Pad((p, 0), padding_mode='edge'), T.Resize(size, BILINEAR) on the PIL
+ * picture, T.ToTensor(), x * 2. - 1., in ONE launch.  T.Resize on a PIL picture is Pillow's two-pass resampling in
+ * 22-bit fixed point, integer arithmetic, so the bytes are reproducible bit for bit.
+ *   src      byte (c) of pixel (y, x) of sample b at src[b * src_sample_stride + y * src_pitch + 3 x + c] (strides in
+ *            bytes, any value, no alignment: a window of a strip is read in place; the sample stride is ignored for
+ *            batch == 1)
+ *   pad      edge replication of pad_x columns left and right and pad_y rows above and below: padded column x reads
+ *            source column min(max(x - pad_x, 0), src_w - 1), rows likewise.  Not a pass; the tables are built for the
+ *            padded sizes in_w = src_w + 2 pad_x, in_h = src_h + 2 pad_y.
+ *   tables   DEVICE int32, per axis: bounds [out][2] = (first tap xmin, taps n), k [out][ksize], built by the caller in
+ *            double (upgpt_amd/prepare.py resample_coeffs): scale = in / out, fs = max(scale, 1), support = fs; for
+ *            output xx: center = (xx + 0.5) scale, xmin = max(int(center - support + 0.5), 0), xmax = min(int(center +
+ *            support + 0.5), in), n = xmax - xmin, w[x] = max(0, 1 - |(x + xmin - center + 0.5) / fs|), divided by
+ *            their sum, k[x] = (int)(w[x] * 2^22 + 0.5).  NULL for both pointers of an axis = that pass is skipped
+ *            (only when in == out; the bytes go through unchanged).  The kernel relies on xmin >= 0, n >= 1 and
+ *            xmin + n <= padded size (n above ksize is cut to ksize); the caller validates before the upload.
+ *   pass     acc = 2^21 + sum_x pix[xmin + x] * k[x], out = min(max(acc >> 22, 0), 255); acc < 2^31 because
+ *            sum k <= 2^22 + n.  The HORIZONTAL pass runs first and is ROUNDED TO uint8; the vertical pass runs on
+ *            those bytes.
+ *   dst_u8   may be NULL: byte (c) of pixel (y, x) of sample b at dst_u8[b * dst_sample_stride + y * dst_pitch + 3 x + c]
+ *   dst_nchw, dst_nhwc   may be NULL: fp32 dense [batch, 3, out_h, out_w] / [batch, out_h, out_w, 3] of
+ *            t = fl(fl(u / 255) * 2 - 1): one correctly rounded fp32 division, an exact doubling, one correctly rounded
+ *            subtraction (the `lr` and `lr_image` entries of the reference's datasets)
+ * A workgroup produces a band of output rows: the horizontal pass of the padded input rows the band's taps cover goes to
+ * LDS as bytes, then a barrier, then the vertical pass from LDS.  The band height (8 rows at most) is chosen so that
+ * the staged rows of 3 out_w bytes fit 64 KiB; a shape for which the yksize rows of ONE output row do not fit returns
+ * UPK_ESHAPE (so does batch > 65535), it is never approximated.  out_w a multiple of 4 with 4-byte aligned dst_u8 /
+ * pitch / sample stride and 16-byte aligned fp32 destinations takes dword / 16-byte stores; everything else is handled
+ * per pixel with the same results.
+ * Errors (UPK_EINVAL): null src, no destination at all, non-positive sizes, negative pads, a missing table pointer on an
+ * axis with in != out (or one of the two given without the other), ksize < 1 on an axis with tables, tables or fp32
+ * destinations not 4-byte aligned, dst_pitch < 3 out_w, overlapping destination samples.  Nothing is launched on an
+ * error.  One launch, class "other".  Never allocates, never synchronises, graph-capturable. */
+int upk_resize_bilinear_u8(upk_ctx* ctx, const uint8_t* src, int batch, int src_h, int src_w, long long src_pitch,
+                           long long src_sample_stride, int pad_x, int pad_y, int out_h, int out_w,
+                           const int32_t* xbounds, const int32_t* xk, int xksize, const int32_t* ybounds,
+                           const int32_t* yk, int yksize, uint8_t* dst_u8, long long dst_pitch,
+                           long long dst_sample_stride, float* dst_nchw, float* dst_nhwc, upk_stream stream);
+
+/* ------------------------------------------------------------------ */
 /* SSIM / MS-SSIM moments of uint8 picture pairs (evaluation metrics).   */
 /* ------------------------------------------------------------------ */
 /* The per-image arithmetic of scripts/eval_metrics.py:110-111 (pytorch_msssim.ssim / ms_ssim with data_range=1,

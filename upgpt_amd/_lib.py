@@ -27,7 +27,7 @@ SYMBOLS = [
     "upk_nchw_f32_to_nhwc_f16", "upk_nhwc_f16_to_nchw_f32", "upk_f32_to_f16", "upk_ddim_step_f32",
     "upk_ddim_step_cfg_f32", "upk_ddim_step_edit_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
     "upk_patchify_nchw_f32_f16", "upk_vit_assemble_f16", "upk_gather_rows_f16",
-    "upk_image_finish_u8", "upk_ssim_ws_bytes", "upk_ssim_u8",
+    "upk_image_finish_u8", "upk_resize_bilinear_u8", "upk_ssim_ws_bytes", "upk_ssim_u8",
     "upk_lpips_input_f16", "upk_relu_pool_nhwc_f16", "upk_lpips_ws_bytes", "upk_lpips_layer_f16",
     "upk_conv2d_rect_f16", "upk_pool3_nhwc_f16", "upk_fid_input_f16", "upk_avgpool_global_f32",
     "upk_advance_step", "upk_step_autoadvance", "upk_kernel_launches", "upk_graph_begin", "upk_graph_end", "upk_graph_launch", "upk_graph_destroy",
@@ -187,6 +187,8 @@ def load_library(path=None):
             "upk_ddpm_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
             "upk_image_finish_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i64, i32, i32, i32, i32, vp, i64, i32, i64, i32,
                                               C.POINTER(C.c_float), vp]),
+            "upk_resize_bilinear_u8": (C.c_int, [vp, vp, i32, i32, i32, i64, i64, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32,
+                                                 vp, i64, i64, vp, vp, vp]),
             "upk_ssim_ws_bytes": (C.c_size_t, [i32, i32, i32, i32]),
             "upk_ssim_u8": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, vp, vp, C.c_size_t, vp]),
             "upk_lpips_input_f16": (C.c_int, [vp, vp, i32, i64, i64, i32, i32, i32, i32, C.POINTER(C.c_float), vp, i64, vp]),
@@ -369,6 +371,16 @@ class Context:
         self._chk(self.lib.upk_image_finish_u8(self.h, _ptr(src), int(layout), int(batch), int(src_h), int(src_w),
                                                int(src_bs), int(top), int(left), int(crop_h), int(crop_w), _ptr(dst),
                                                int(pitch), int(dst_x), int(dst_bs), int(mode), dm, self._s()))
+
+    def resize_bilinear(self, src, batch, src_h, src_w, src_pitch, src_ss, pad_x, pad_y, out_h, out_w, xtab, ytab,
+                        dst_u8=None, dst_pitch=0, dst_ss=0, dst_nchw=None, dst_nhwc=None):
+        """upk_resize_bilinear_u8; xtab / ytab: (bounds, k, ksize) of device int32 tensors, or None for a skipped pass."""
+        xb, xk, xks = xtab if xtab is not None else (None, None, 0)
+        yb, yk, yks = ytab if ytab is not None else (None, None, 0)
+        self._chk(self.lib.upk_resize_bilinear_u8(self.h, _ptr(src), int(batch), int(src_h), int(src_w), int(src_pitch),
+                                                  int(src_ss), int(pad_x), int(pad_y), int(out_h), int(out_w), _ptr(xb),
+                                                  _ptr(xk), int(xks), _ptr(yb), _ptr(yk), int(yks), _ptr(dst_u8),
+                                                  int(dst_pitch), int(dst_ss), _ptr(dst_nchw), _ptr(dst_nhwc), self._s()))
 
     def ssim_ws_bytes(self, batch, h, w, levels):
         return self.lib.upk_ssim_ws_bytes(int(batch), int(h), int(w), int(levels))

@@ -11,6 +11,9 @@ run_metrics is the step after it (scripts/eval_metrics.py): results/gt against r
 metrics.txt with per-image SSIM and MS-SSIM from upk_ssim_u8 (upgpt_amd/metrics.py) and, given the two
 public weight files, LPIPS (upgpt_amd/lpips.py) and, given pytorch_fid's Inception weights, the FID line of
 metrics.txt (upgpt_amd/fid.py); `python -m upgpt_amd.evaluate --dir <save_dir>/results` runs it.
+
+run_upscale is the second model's pass over a results tree: results/samples-sized pictures -> the `lr` conditioning on the
+device (upgpt_amd/prepare.py, upk_resize_bilinear_u8) -> the upscale model -> results/upscaled.
 """
 import os
 from pathlib import Path
@@ -184,6 +187,75 @@ def run_test(model, batches, save_dir, **log_kwargs):
             model.logger = prev
         else:
             del model.logger
+    return Path(save_dir) / "results"
+
+
+def run_upscale(model, batches, lr_dir, save_dir, pad=(8, 0), **log_kwargs):
+    """The second stage of an evaluation run, the flow of the reference's DeepFashionSuperResSampling dataset
+    (deepfashion_inshop.py:419-479) through the upscale model: for every batch dict (`fname`, `styles`, `txt`, `image`)
+    the low-resolution pictures lr_dir/<fname>.jpg are decoded by PIL, uploaded as bytes and turned into batch['lr']
+    [B, 3, h, w] and batch['lr_image'] [B, h, w, 3] ON THE DEVICE by one upk_resize_bilinear_u8 launch
+    (prepare.lr_transform with the dataset's pad of 8 columns, [h, w] = model.image_size); then
+    model.log_images(batch, N=<batch size>, **LOG_DEFAULTS, use_ema=model.use_ema, **log_kwargs), and log['samples']
+    finished by upk_image_finish_u8 (FINISH_SAMPLE, centre-cropped to model.crop_size).  The samples and the resized
+    conditioning bytes share one device buffer that crosses to the host in one copy behind one synchronise, as in
+    finished_arrays.  Written: save_dir/results/upscaled/<fname>.jpg and, the conditioning actually used,
+    save_dir/results/lr/<fname>.jpg.  Returns the results directory.  The caller's batch dicts are left as they came.
+
+    This is THIS PACKAGE'S extension: the reference's own test_step cannot run on that dataset's batches, because it
+    reads `smpl_image` and `src_image`, which the dataset does not provide.  N is the batch size here, unlike
+    test_step's len(batch).  A missing or unreadable (or differently sized) lr file raises ValueError naming the file;
+    it is not silently replaced by the next sample, as the reference's loader would do."""
+    from PIL import Image
+
+    from . import prepare
+    lr_dir = Path(lr_dir)
+    roots = {k: Path(save_dir) / "results" / k for k in ("upscaled", "lr")}
+    for r in roots.values():
+        os.makedirs(str(r), exist_ok=True)
+    dev = model.device
+    oh, ow = (int(v) for v in model.image_size)
+    f = 2 ** int(model.num_downs)
+    win = center_crop_window(f * oh, f * ow, model.crop_size)
+    ch, cw = win[2], win[3]
+    for batch in batches:
+        names = list(batch["fname"])
+        n = len(names)
+        pics = []
+        for fname in names:
+            path = lr_dir / f"{fname}.jpg"
+            arr = _decode(path) if path.is_file() else None
+            require(arr is not None, "run_upscale: cannot read the low-resolution picture %s" % path, ValueError)
+            require(not pics or arr.shape == pics[0].shape, "run_upscale: %s is %s, the first picture of its batch %s" % (
+                path, arr.shape, pics[0].shape if pics else None), ValueError)
+            pics.append(arr)
+        off_lr = (n * ch * cw * 3 + 15) // 16 * 16
+        total = off_lr + n * oh * ow * 3
+        buf = torch.empty(total, dtype=torch.uint8, device=dev)
+        up_view = buf[:n * ch * cw * 3].view(n, ch, cw, 3)
+        lr_view = buf[off_lr:].view(n, oh, ow, 3)
+        src = torch.from_numpy(np.stack(pics)).to(dev, non_blocking=True)
+        kw = dict(LOG_DEFAULTS, N=n, use_ema=model.use_ema)
+        kw.update(log_kwargs)
+        with torch.no_grad():
+            lr, lr_image = prepare.lr_transform(src, [oh, ow], pad, out_u8=lr_view)
+            log = model.log_images(dict(batch, lr=lr, lr_image=lr_image), **kw)
+            samples = log["samples"]
+            require(tuple(samples.shape[1:]) == (3, f * oh, f * ow), "run_upscale: samples %s, expected [n, 3, %d, %d]" % (
+                tuple(samples.shape), f * oh, f * ow), ValueError)
+            m = min(int(samples.shape[0]), n)
+            finish_images(samples[:m].to(dev, torch.float32), up_view[:m], _lib.LAYOUT_NCHW, _lib.FINISH_SAMPLE, window=win)
+        host = torch.empty(total, dtype=torch.uint8, pin_memory=buf.is_cuda)
+        host.copy_(buf, non_blocking=True)
+        if buf.is_cuda:
+            torch.cuda.current_stream(dev).synchronize()
+        arr = host.numpy()
+        up_arr = arr[:n * ch * cw * 3].reshape(n, ch, cw, 3)
+        lr_arr = arr[off_lr:].reshape(n, oh, ow, 3)
+        for i, fname in enumerate(names):
+            if i < m:
+                Image.fromarray(up_arr[i]).save(roots["upscaled"] / f"{fname}.jpg")
+            Image.fromarray(lr_arr[i]).save(roots["lr"] / f"{fname}.jpg")
     return Path(save_dir) / "results"
 
 

@@ -187,6 +187,37 @@ class InferenceModel:
             out[k] = v.permute(0, 2, 3, 1).numpy() * 0.5 + 0.5
         return out
 
+    def upscale(self, pictures, styles, txt, steps=200, pad=(4, 0), use_ema=False, image=None):
+        """The demo's "Upscale" button (app.py:387-399), called on the InferenceModel that holds the upscale checkpoint:
+        low-resolution pictures -> generate()'s dict, 'samples' float numpy [B, f H, f W, 3] in [0, 1] with [H, W] the
+        model's image_size and f = 2 ** num_downs (512 x 384 for the reference's config).
+        pictures: uint8 [B, h, w, 3], a device tensor (the bytes upk_image_finish_u8 wrote are taken in place), a host
+        array / tensor, or a list of PIL images of one size; styles: [B, 9, 768] or [9, 768], mix_style's output; txt: a
+        string or a list of B strings.  batch['lr'] is prepare.lr_transform(pictures, image_size, pad)[0], the
+        reference's lr_transform (pad 4 columns by edge replication, bilinear resize as Pillow does it, ToTensor,
+        x * 2 - 1) in one launch on the device; batch['image'] defaults to zeros [B, f H, f W, 3], standing in for the
+        dummy picture the demo loads (only its shape matters outside the reconstruction).  As with generate, log_images'
+        default N = 8 caps the samples of one call."""
+        from . import prepare
+        if isinstance(pictures, (list, tuple)):
+            pictures = np.stack([np.asarray(p.convert("RGB") if hasattr(p, "convert") else p, dtype=np.uint8) for p in pictures])
+        lr = prepare.lr_transform(pictures, self.model.image_size, pad)[0]
+        n = int(lr.shape[0])
+        styles = torch.as_tensor(styles)
+        if styles.dim() == 2:
+            styles = styles.unsqueeze(0).repeat(n, 1, 1)
+        if isinstance(txt, str):
+            txt = [txt] * n
+        elif not torch.is_tensor(txt):  # (a tensor: embeddings for a model whose text stage is a pass-through)
+            txt = list(txt)
+        if styles.shape[0] != n or len(txt) != n:
+            raise ValueError("upscale: %d pictures, %d styles, %d texts" % (n, styles.shape[0], len(txt)))
+        if image is None:
+            f = 2 ** self.model.num_downs
+            image = torch.zeros(n, f * self.model.image_size[0], f * self.model.image_size[1], 3, device=lr.device)
+        batch = {'image': image, 'lr': lr, 'styles': styles.to(lr.device), 'txt': txt}
+        return self.generate(batch, steps, use_ema=use_ema)
+
     def mix_style(self, s, w, mask=[]):
         """Style embeddings [9, 768] of the crops `s` [9, 3, 224, 224]; slots named in `mask` are blanked (in `s`
         itself, as the reference does) and slots with a text in `w` take the CLIP TEXT embedding instead (:173-189)."""
