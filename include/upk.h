@@ -627,6 +627,78 @@ int upk_resize_bilinear_u8(upk_ctx* ctx, const uint8_t* src, int batch, int src_
                            long long dst_sample_stride, float* dst_nchw, float* dst_nhwc, upk_stream stream);
 
 /* ------------------------------------------------------------------ */
+/* Style crops: picture + human-parsing label map -> batch['styles'].    */
+/* ------------------------------------------------------------------ */
+/* The reference's Segmenter.forward (segm_utils.py:42-150) followed by the consumer's clip_transform
+ * (deepfashion_inshop.py:128-133), in TWO launches with no device-to-host copy between them: the cut of every group is
+ * found on the device and read from device memory by the second launch, so the pair is graph-capturable and a replay
+ * on new label maps gives the new crops.
+ *   pictures  uint8, byte (c) of pixel (y, x) of sample b at pictures[b * pic_sample_stride + y * pic_pitch + 3 x + c]
+ *   segm      uint8 label maps, label of pixel (y, x) at segm[b * segm_sample_stride + y * segm_pitch + x]
+ *             (strides in bytes, no alignment; pic_pitch >= 3 w, segm_pitch >= w; sample strides are ignored for
+ *             batch == 1)
+ *   label_groups_host   HOST uint32 [256], read during the call and handed to the kernel by value: bit g of entry l
+ *             is set when label l belongs to group g (a label may belong to several groups); n_groups <= 32
+ *
+ * upk_segm_boxes_u8: boxes[b][g][8] (DEVICE int32) = left, right, top, bottom, N, S_r, S_g, S_b of mask = (label in
+ * group g).  left / top are the first column / row holding a mask pixel, right / bottom the INDEX OF THE LAST one
+ * (the reference's get_mask_range with margin 0; used below as exclusive ends, so the last masked column and row are
+ * cut off, as in the reference).  N is the number of mask pixels and S_c the integer sum of channel c over them.  With
+ * no mask pixel the record is 0, w, 0, h, 0, 0, 0, 0.  Integers only: the result does not depend on reduction order.
+ *
+ * upk_style_crops_u8: one crop of 224 x 224 per (sample, slot).
+ *   slot_groups_host    HOST int32 [n_slots] (n_slots <= 32): the group a slot shows, -1 for an empty slot
+ *   group_flags_host    HOST int32 [n_groups]: UPK_STYLE_FILL | UPK_STYLE_MASK | max_rows << 8
+ *   mean_std_host       HOST float [6] = mean[3], std[3] of the normalisation (std > 0)
+ *   per crop, from the group's record:
+ *     UPK_STYLE_FILL (the reference's `background`): no cut and no pad; the content is the whole picture with every
+ *       pixel outside the mask replaced, per channel, by floor(S_c / N).  Invalid when N == 0.
+ *     otherwise: the content is the picture, with pixels outside the mask zeroed when UPK_STYLE_MASK is set (every
+ *       group but `face`), cut to rows [top, bottom) and columns [left, right): ch x cw.  Invalid when ch <= 0 or
+ *       cw <= 0, or when max_rows > 0 and ch > max_rows (`face`: 128).  p = floor((ch - cw) / 2): p > 0 adds p zero
+ *       columns left and right, p < 0 adds -p zero rows above and below (ch - cw = -3 pads 2 and 2).
+ *     T.Resize(224) of the padded ph x pw content: the short side becomes 224, the long one 224 * long / short (integer
+ *       division; equal to Python's int(224 * long / short) for these sizes); nothing changes when short == 224.  The
+ *       resize is upk_resize_bilinear_u8's: Pillow's tables, the horizontal pass first and rounded to uint8.  The
+ *       tables of the produced rows and columns are built IN THE KERNEL in double, operation for operation as stated
+ *       above for the caller of upk_resize_bilinear_u8, without contraction.
+ *     T.CenterCrop(224): offset int(round((n - 224) / 2.0)) with round-half-to-even (227 -> 2, 225 -> 0).  Only the
+ *       central 224 rows / columns are computed.
+ *   dst_u8    may be NULL: dense uint8 [batch, n_slots, 224, 224, 3], the crop's bytes
+ *   dst_f32   may be NULL: dense fp32 [batch, n_slots, 3, 224, 224] of t = fl(fl(fl(u / 255) - mean_c) / std_c),
+ *             three correctly rounded fp32 operations (T.ToTensor, T.Normalize)
+ *   valid     DEVICE int32 [batch, n_slots]: 1 for a crop made as above, 0 for an empty slot or an invalid crop; those
+ *             get bytes 0 and t(0).  Validity is geometric: a valid cut that is black everywhere stays valid with the
+ *             zero bytes the reference returns for it.
+ *   coeff_out may be NULL: DEVICE int32 [batch, n_slots, 2, 224, 18], axis 0 = rows, 1 = columns, per produced index
+ *             (first tap, taps, k[16]) as the kernel used them (a skipped pass is the single tap (index, 1, 2^22));
+ *             zeros for an empty slot or an invalid crop.  For tests: it tells a wrong table from a wrong pass.
+ * Two deliberate differences from the reference's file flow: the crop's bytes are handed on as they are (the reference
+ * stores every crop as a JPEG and decodes it again), and the fill colour is the exact floor(S_c / N) where the reference
+ * truncates a float32 mean of u / 255 values times 255 (equal except where rounding noise decides, e.g. a mean that is
+ * an exact integer).
+ * A workgroup makes 8 output rows of one crop: coefficients, then the horizontal pass of the input rows its taps cover
+ * into LDS as bytes, a barrier, and the vertical pass from LDS.  Sides up to 1344 (scale <= 6: at most 14 taps and 56
+ * staged rows of 672 bytes) are supported; a larger picture returns UPK_ESHAPE (so does batch > 65535).
+ * Errors (UPK_EINVAL): a null pointer where none is allowed, no destination at all, non-positive sizes, n_groups
+ * outside 1 .. 32, n_slots outside 1 .. 32, a slot naming a group outside -1 .. n_groups - 1, negative flags, std <= 0,
+ * pic_pitch < 3 w, segm_pitch < w, boxes / valid / coeff_out / dst_f32 not 4-byte aligned.  Nothing is launched on an
+ * error.  One launch each, class "other".  Never allocate, never synchronise, graph-capturable. */
+#define UPK_STYLE_FILL 0x1
+#define UPK_STYLE_MASK 0x2
+#define UPK_STYLE_MAX_GROUPS 32
+#define UPK_STYLE_MAX_SLOTS 32
+int upk_segm_boxes_u8(upk_ctx* ctx, const uint8_t* segm, long long segm_pitch, long long segm_sample_stride,
+                      const uint8_t* pictures, long long pic_pitch, long long pic_sample_stride, int batch, int h, int w,
+                      const uint32_t* label_groups_host, int n_groups, int32_t* boxes, upk_stream stream);
+int upk_style_crops_u8(upk_ctx* ctx, const uint8_t* pictures, long long pic_pitch, long long pic_sample_stride,
+                       const uint8_t* segm, long long segm_pitch, long long segm_sample_stride, int batch, int h, int w,
+                       const uint32_t* label_groups_host, int n_groups, const int32_t* boxes,
+                       const int32_t* group_flags_host, const int32_t* slot_groups_host, int n_slots,
+                       const float* mean_std_host, uint8_t* dst_u8, float* dst_f32, int32_t* valid, int32_t* coeff_out,
+                       upk_stream stream);
+
+/* ------------------------------------------------------------------ */
 /* SSIM / MS-SSIM moments of uint8 picture pairs (evaluation metrics).   */
 /* ------------------------------------------------------------------ */
 /* The per-image arithmetic of scripts/eval_metrics.py:110-111 (pytorch_msssim.ssim / ms_ssim with data_range=1,

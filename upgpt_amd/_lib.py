@@ -27,7 +27,7 @@ SYMBOLS = [
     "upk_nchw_f32_to_nhwc_f16", "upk_nhwc_f16_to_nchw_f32", "upk_f32_to_f16", "upk_ddim_step_f32",
     "upk_ddim_step_cfg_f32", "upk_ddim_step_edit_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
     "upk_patchify_nchw_f32_f16", "upk_vit_assemble_f16", "upk_gather_rows_f16",
-    "upk_image_finish_u8", "upk_resize_bilinear_u8", "upk_ssim_ws_bytes", "upk_ssim_u8",
+    "upk_image_finish_u8", "upk_resize_bilinear_u8", "upk_segm_boxes_u8", "upk_style_crops_u8", "upk_ssim_ws_bytes", "upk_ssim_u8",
     "upk_lpips_input_f16", "upk_relu_pool_nhwc_f16", "upk_lpips_ws_bytes", "upk_lpips_layer_f16",
     "upk_conv2d_rect_f16", "upk_pool3_nhwc_f16", "upk_fid_input_f16", "upk_avgpool_global_f32",
     "upk_advance_step", "upk_step_autoadvance", "upk_kernel_launches", "upk_graph_begin", "upk_graph_end", "upk_graph_launch", "upk_graph_destroy",
@@ -38,6 +38,7 @@ SYMBOLS = [
 F_SILU, F_GEGLU, F_OUT_F32, F_OUT_NCHW_F32, F_UPSAMPLE2X, F_PAD_ASYM = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 DDPM_X0, DDPM_CLIP = 0x1, 0x2  # upk_ddpm_step_f32 flags
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1  # upk_image_finish_u8 source layouts
+STYLE_FILL, STYLE_MASK = 0x1, 0x2  # upk_style_crops_u8 group flags (max_rows << 8 is or-ed in)
 FINISH_SAMPLE, FINISH_INPUT, FINISH_DENORM = 0, 1, 2  # ... and arithmetic modes
 F_QUICKGELU = 0x40
 POOL_MAX, POOL_AVG = 0, 1  # upk_pool3_nhwc_f16 modes
@@ -189,6 +190,10 @@ def load_library(path=None):
                                               C.POINTER(C.c_float), vp]),
             "upk_resize_bilinear_u8": (C.c_int, [vp, vp, i32, i32, i32, i64, i64, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32,
                                                  vp, i64, i64, vp, vp, vp]),
+            "upk_segm_boxes_u8": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, i32, i32, i32, C.POINTER(C.c_uint32), i32, vp, vp]),
+            "upk_style_crops_u8": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, i32, i32, i32, C.POINTER(C.c_uint32), i32, vp,
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, C.POINTER(C.c_float), vp, vp, vp,
+                                             vp, vp]),
             "upk_ssim_ws_bytes": (C.c_size_t, [i32, i32, i32, i32]),
             "upk_ssim_u8": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, vp, vp, C.c_size_t, vp]),
             "upk_lpips_input_f16": (C.c_int, [vp, vp, i32, i64, i64, i32, i32, i32, i32, C.POINTER(C.c_float), vp, i64, vp]),
@@ -381,6 +386,25 @@ class Context:
                                                   int(src_ss), int(pad_x), int(pad_y), int(out_h), int(out_w), _ptr(xb),
                                                   _ptr(xk), int(xks), _ptr(yb), _ptr(yk), int(yks), _ptr(dst_u8),
                                                   int(dst_pitch), int(dst_ss), _ptr(dst_nchw), _ptr(dst_nhwc), self._s()))
+
+    def segm_boxes(self, segm, segm_pitch, segm_ss, pictures, pic_pitch, pic_ss, batch, h, w, label_groups, n_groups, boxes):
+        """upk_segm_boxes_u8; label_groups: 256 host integers, bit g of entry l = label l belongs to group g."""
+        lg = None if label_groups is None else (C.c_uint32 * 256)(*[int(v) for v in label_groups])
+        self._chk(self.lib.upk_segm_boxes_u8(self.h, _ptr(segm), int(segm_pitch), int(segm_ss), _ptr(pictures), int(pic_pitch),
+                                             int(pic_ss), int(batch), int(h), int(w), lg, int(n_groups), _ptr(boxes), self._s()))
+
+    def style_crops(self, pictures, pic_pitch, pic_ss, segm, segm_pitch, segm_ss, batch, h, w, label_groups, n_groups, boxes,
+                    group_flags, slot_groups, mean_std, dst_u8=None, dst_f32=None, valid=None, coeff_out=None):
+        """upk_style_crops_u8; group_flags (STYLE_FILL | STYLE_MASK | max_rows << 8 per group), slot_groups (-1: empty)
+        and mean_std (mean[3], std[3]) are host sequences."""
+        lg = None if label_groups is None else (C.c_uint32 * 256)(*[int(v) for v in label_groups])
+        gf = None if group_flags is None else (C.c_int32 * max(len(group_flags), 1))(*[int(v) for v in group_flags])
+        sl = None if slot_groups is None else (C.c_int32 * max(len(slot_groups), 1))(*[int(v) for v in slot_groups])
+        ms = None if mean_std is None else (C.c_float * 6)(*[float(v) for v in mean_std])
+        self._chk(self.lib.upk_style_crops_u8(self.h, _ptr(pictures), int(pic_pitch), int(pic_ss), _ptr(segm), int(segm_pitch),
+                                              int(segm_ss), int(batch), int(h), int(w), lg, int(n_groups), _ptr(boxes), gf, sl,
+                                              0 if slot_groups is None else len(slot_groups), ms, _ptr(dst_u8), _ptr(dst_f32),
+                                              _ptr(valid), _ptr(coeff_out), self._s()))
 
     def ssim_ws_bytes(self, batch, h, w, levels):
         return self.lib.upk_ssim_ws_bytes(int(batch), int(h), int(w), int(levels))

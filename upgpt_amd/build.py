@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.environ.get("UPK_LIB") or os.path.join(HERE, "libupk.so")  # (UPK_LIB + UPK_CXXFLAGS: dev builds)
 SOURCES = ["igemm.hip", "bigtile.hip", "astat.hip", "mlp.hip", "xblock.hip", "attention.hip", "norm.hip", "misc.hip", "image.hip",
-           "metrics.hip", "lpips.hip", "inception.hip", "resize.hip"]
+           "metrics.hip", "lpips.hip", "inception.hip", "resize.hip", "styles.hip"]
 # per-file flags.  attention.hip: MFMA results straight into arch VGPRs — the softmax between the two matmuls reads
 # every score with VALU instructions, and with the accumulators in AGPRs 112 of ~600 issue slots per 64-key tile were
 # v_accvgpr moves (the kernels use < 128 registers, there is nothing to gain from the AGPR file)
@@ -26,9 +26,12 @@ SOURCES = ["igemm.hip", "bigtile.hip", "astat.hip", "mlp.hip", "xblock.hip", "at
 # lpips.hip: upk_lpips_input_f16 is specified the same way (bit for bit torch's fp32 expression, then .half())
 # inception.hip: upk_fid_input_f16 likewise (one IEEE fp32 operation at a time)
 # resize.hip: upk_resize_bilinear_u8's fp32 finishing likewise (u / 255, * 2, - 1)
+# styles.hip: upk_style_crops_u8 builds Pillow's coefficient tables in double, one IEEE operation at a time, and
+# normalises the same way (u / 255, - mean, / std)
 FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans", "-mno-amdgpu-ieee"],
               "image.hip": ["-ffp-contract=off"], "lpips.hip": ["-ffp-contract=off"],
-              "inception.hip": ["-ffp-contract=off"], "resize.hip": ["-ffp-contract=off"]}
+              "inception.hip": ["-ffp-contract=off"], "resize.hip": ["-ffp-contract=off"],
+              "styles.hip": ["-ffp-contract=off"]}
 ARCH = "gfx950"
 
 

@@ -259,6 +259,52 @@ def run_upscale(model, batches, lr_dir, save_dir, pad=(8, 0), **log_kwargs):
     return Path(save_dir) / "results"
 
 
+def run_styles(image_root, segm_root, dst_root, segmenter='mm', batch_size=16):
+    """The flow the reference's scripts/segment.py intends: for every label map segm_root/**/<id>_segm.png and its picture
+    image_root/**/<id>.jpg the style crops are made ON THE DEVICE (styles.style_crops: two launches per batch, pictures
+    of equal size batched up to `batch_size`) and every VALID group's crop is written from the device bytes to
+    dst_root/**/<id with its first '_' turned into '/'>/<group>.jpg with Pillow's default save, the files the
+    reference's datasets read back as batch['styles'].  An invalid crop (an empty cut, a face of more than 128 rows, a
+    background without a pixel) writes no file, which the datasets read as the empty style.  Returns the number of
+    label maps processed.  An unreadable picture or label map, or a pair of different sizes, raises ValueError naming
+    the file."""
+    from PIL import Image
+
+    from . import styles
+    seg = styles.get_segmenter(segmenter)
+    segm_root, image_root, dst_root = Path(segm_root), Path(image_root), Path(dst_root)
+    by_size = {}
+    for segm_file in sorted(segm_root.rglob("*_segm.png")):
+        rel = segm_file.relative_to(segm_root)
+        stem = rel.name[:-len("_segm.png")]
+        image_file = image_root / rel.parent / (stem + ".jpg")
+        try:
+            with Image.open(str(segm_file)) as im:
+                segm = np.asarray(im, dtype=np.uint8)
+        except Exception:
+            segm = None
+        require(segm is not None and segm.ndim == 2, "run_styles: cannot read the label map %s" % segm_file, ValueError)
+        pic = _decode(image_file) if image_file.is_file() else None
+        require(pic is not None, "run_styles: cannot read the picture %s" % image_file, ValueError)
+        require(pic.shape[:2] == segm.shape, "run_styles: %s is %s, its label map %s" % (image_file, pic.shape[:2], segm.shape),
+                ValueError)
+        by_size.setdefault(segm.shape, []).append((dst_root / rel.parent / stem.replace('_', '/', 1), pic, segm))
+    done = 0
+    for items in by_size.values():
+        for i in range(0, len(items), int(batch_size)):
+            part = items[i:i + int(batch_size)]
+            _, valid, u8 = styles.style_crops(np.stack([p for _, p, _ in part]), np.stack([s for _, _, s in part]), seg,
+                                              seg.names, out_u8=True)
+            valid, u8 = valid.cpu().numpy(), u8.cpu().numpy()
+            for j, (dst_dir, _, _) in enumerate(part):
+                os.makedirs(str(dst_dir), exist_ok=True)
+                for g, name in enumerate(seg.names):
+                    if valid[j, g]:
+                        Image.fromarray(u8[j, g]).save(dst_dir / (name + ".jpg"))
+            done += len(part)
+    return done
+
+
 def _decode(path):
     """uint8 [H, W, 3] of an image file, or None when it cannot be read."""
     from PIL import Image

@@ -218,6 +218,22 @@ class InferenceModel:
         batch = {'image': image, 'lr': lr, 'styles': styles.to(lr.device), 'txt': txt}
         return self.generate(batch, steps, use_ema=use_ema)
 
+    def extract_styles(self, picture, segm, segmenter='lip'):
+        """The style crops of ONE source picture, ready for mix_style: fp32 [9, 3, 224, 224] on the device, one crop per
+        entry of style_names, CLIP-normalised.  The reference's Segmenter.forward (segm_utils.py) and clip_transform,
+        made by styles.style_crops in two launches on the device, without the reference's <style>.jpg files in between.
+        picture: uint8 [H, W, 3] (a PIL image, a host array or a tensor; a device tensor is read in place); segm: the
+        human-parsing label map uint8 [H, W] of the same size; segmenter: 'lip' (eight groups), 'mm' (face, background,
+        skin) or a styles.Segmenter.  A style the segmenter does not produce, or whose cut is empty, is the empty
+        style clip_norm(0)."""
+        from . import styles
+
+        def as_map(v, mode):
+            if hasattr(v, "convert"):  # a PIL image
+                v = np.asarray(v.convert(mode) if mode == "RGB" else v, dtype=np.uint8)
+            return v[None] if isinstance(v, np.ndarray) or torch.is_tensor(v) else v
+        return styles.style_crops(as_map(picture, "RGB"), as_map(segm, None), segmenter, style_names)[0][0]
+
     def mix_style(self, s, w, mask=[]):
         """Style embeddings [9, 768] of the crops `s` [9, 3, 224, 224]; slots named in `mask` are blanked (in `s`
         itself, as the reference does) and slots with a text in `w` take the CLIP TEXT embedding instead (:173-189)."""
