@@ -273,7 +273,9 @@ int upk_geglu_mlp_supported(upk_ctx* ctx, const upk_mlp_desc* d);
  * [heads * d rows][K = c] with the LayerNorm affine folded in (as ln_colsum weights); vec = [b_out1 (c) | colsum_q
  * (heads * d) | bias_q (heads * d) | b_out2 (c)] fp32, zero padded to a multiple of 256 floats; k_ctx [batch * n_kv, ldk],
  * vt_ctx [batch, heads, d, vt_ld] as upk_attention_f16 takes them (n_kv <= 96 <= vt_ld).  hw = rows per sample (a
- * multiple of rows_per_wg: 16 or 32, 0 = 32).  Shapes: heads = 8, (c, d) in {(224, 32), (448, 64)}. */
+ * multiple of rows_per_wg: 16 or 32, 0 = 32; (c, d) = (224, 32) also 64 and 128 — m / 128 workgroups that stream the
+ * weights a quarter as often, for launches that share the chip with other batches; the tile must fit 160 KB of LDS).
+ * Shapes: heads = 8, (c, d) in {(224, 32), (448, 64)}. */
 typedef struct upk_xblock_desc {
   const void* a1;
   int32_t lda, m, c, heads, d;
@@ -303,7 +305,7 @@ int upk_cross_block_supported(upk_ctx* ctx, const upk_xblock_desc* d);
  * [3 heads d rows][K = c] in q | k | v order at the padded head width, LayerNorm affine folded in; vec = [b_in (c) |
  * colsum_qkv (3 heads d) | bias_qkv (3 heads d)] fp32, zero padded to a multiple of 256 floats.  t0 [m, ld_t0];
  * qk [m, ld_qk] = q | k; vt [m / hw, heads, d, vt_ld] = v transposed (vt_ld >= hw).  hw = rows per sample, a multiple of
- * rows_per_wg (16 or 32, 0 = 32).  Shapes: heads = 8, c = 224, d = 32. */
+ * rows_per_wg (16, 32, 64 or 128, 0 = 32; 64 and 128 as for upk_cross_block_f16).  Shapes: heads = 8, c = 224, d = 32. */
 typedef struct upk_hblock_desc {
   const void* x;
   int32_t ldx, m, c, heads, d;

@@ -674,7 +674,21 @@ struct XbCfg {
   void (*fn)(const XbArgs);
   unsigned long long attr_done;  // (devices on which the LDS attribute is set)
 };
+constexpr size_t XB_LDS_MAX = 160 * 1024;  // what upk_lds_attr_once asks for
+size_t xb_lds_bytes(int c, int hd, int bm) {
+  const int vec_pieces = (2 * c + 2 * hd + 255) / 256;
+  return (size_t)(hd / 32 + c / 32) * bm * 64 + (size_t)bm * 8 + (size_t)vec_pieces * 1024;
+}
+size_t hb_lds_bytes(int c, int hd, int bm, bool gnf) {
+  const int vec_pieces = (c + 6 * hd + 255) / 256;
+  return (size_t)2 * (c / 32) * bm * 64 + (size_t)bm * 8 + (size_t)vec_pieces * 1024 +
+         (gnf ? (size_t)2 * c * 4 + 2 * UPK_GN_GROUPS_MAX * 8 + 2 * UPK_GN_GROUPS_MAX * 4 : 0);
+}
+// the 128-row form: a 4-deep ring for the to_out weights (237 VGPRs; 8 deep it takes all 256 and spills 11 to scratch)
+constexpr int XB128_PF1 = 4;
 XbCfg g_xb[] = {
+    {224, 32, 128, xblock_kernel<8, 7, 32, XB128_PF1, 7>, 0},
+    {224, 32, 64, xblock_kernel<4, 7, 32, 8, 7>, 0},
     {224, 32, 32, xblock_kernel<2, 7, 32, 8, 7>, 0},
     {224, 32, 16, xblock_kernel<1, 7, 32, 8, 7>, 0},
     {448, 64, 32, xblock_kernel<2, 14, 64, 4, 2>, 0},
@@ -694,6 +708,7 @@ extern "C" int upk_cross_block_supported(upk_ctx* ctx, const upk_xblock_desc* d)
   if (!xb_find(d)) return 0;
   const int bm = d->rows_per_wg > 0 ? d->rows_per_wg : 32;
   if (d->hw <= 0 || d->hw % bm || d->m % d->hw) return 0;
+  if (xb_lds_bytes(d->c, d->heads * d->d, bm) > XB_LDS_MAX) return 0;
   if ((d->lda & 7) || (d->ld_t0 & 3) || (d->ldy & 3) || (d->ldk & 3) || (d->vt_ld & 3)) return 0;
   return 1;
 }
@@ -724,19 +739,31 @@ extern "C" int upk_cross_block_f16(upk_ctx* ctx, const upk_xblock_desc* d, upk_s
   s.dbg = getenv("UPK_XB_TL") ? (unsigned long long*)((char*)ctx->ws + ctx->ws_bytes - 4096) : nullptr;
 #endif
   const int bm = cfg->bm;
-  const size_t lds = (size_t)(hd / 32 + d->c / 32) * bm * 64 + (size_t)bm * 8 + (size_t)s.vec_pieces * 1024;
+  const size_t lds = xb_lds_bytes(d->c, hd, bm);
   if (int rc = upk_lds_attr_once(ctx, (const void*)cfg->fn, &cfg->attr_done)) return rc;
   upk_prof_scope prof(ctx, UPK_CLS_ATTN, stream);
   hipLaunchKernelGGL(cfg->fn, dim3(d->m / bm), dim3(512), lds, stream, s);
   return upk_check_launch(ctx, "cross_block");
 }
 
+namespace {
+// rows per workgroup -> index of the hblock_kernel instantiation pair (GroupNorm fold off / on), -1 = none
+int hb_variant(int bm) { return bm == 32 ? 0 : bm == 16 ? 1 : bm == 64 ? 2 : bm == 128 ? 3 : -1; }
+void (*const g_hb[4][2])(const HbArgs) = {
+    {hblock_kernel<2, 7, 32, false>, hblock_kernel<2, 7, 32, true>},
+    {hblock_kernel<1, 7, 32, false>, hblock_kernel<1, 7, 32, true>},
+    {hblock_kernel<4, 7, 32, false>, hblock_kernel<4, 7, 32, true>},
+    {hblock_kernel<8, 7, 32, false>, hblock_kernel<8, 7, 32, true>},
+};
+}  // namespace
+
 extern "C" int upk_head_block_supported(upk_ctx* ctx, const upk_hblock_desc* d) {
   if (!ctx || !d) return 0;
   if (d->heads != XB_NW || d->c != 224 || d->d != 32) return 0;
   const int bm = d->rows_per_wg > 0 ? d->rows_per_wg : 32;
-  if (bm != 32 && bm != 16) return 0;
+  if (hb_variant(bm) < 0) return 0;
   if (d->hw <= 0 || d->hw % bm || d->m % d->hw || d->vt_ld < d->hw) return 0;
+  if (hb_lds_bytes(d->c, d->heads * d->d, bm, true) > XB_LDS_MAX) return 0;
   if ((d->ldx & 7) || (d->ld_t0 & 3) || (d->ld_qk & 3)) return 0;
   return 1;
 }
@@ -771,12 +798,11 @@ extern "C" int upk_head_block_f16(upk_ctx* ctx, const upk_hblock_desc* d, upk_st
     s.gn_part = d->gn_part, s.gn_gamma = d->gn_gamma, s.gn_beta = d->gn_beta;
     s.gn_nblk = d->gn_nblk, s.gn_ld = d->gn_ld, s.gn_cpg = d->c / d->gn_groups, s.gn_eps = d->gn_eps;
   }
-  void (*fn)(const HbArgs) = bm == 32 ? (gnf ? hblock_kernel<2, 7, 32, true> : hblock_kernel<2, 7, 32, false>)
-                                      : (gnf ? hblock_kernel<1, 7, 32, true> : hblock_kernel<1, 7, 32, false>);
-  const size_t lds = (size_t)2 * (d->c / 32) * bm * 64 + (size_t)bm * 8 + (size_t)s.vec_pieces * 1024 +
-                     (gnf ? (size_t)2 * d->c * 4 + 2 * UPK_GN_GROUPS_MAX * 8 + 2 * UPK_GN_GROUPS_MAX * 4 : 0);
-  static unsigned long long hb_attr[4] = {};
-  if (int rc = upk_lds_attr_once(ctx, (const void*)fn, &hb_attr[(bm == 32 ? 0 : 2) + (gnf ? 1 : 0)])) return rc;
+  const int var = hb_variant(bm);
+  void (*fn)(const HbArgs) = g_hb[var][gnf ? 1 : 0];
+  const size_t lds = hb_lds_bytes(d->c, hd, bm, gnf);
+  static unsigned long long hb_attr[4][2] = {};
+  if (int rc = upk_lds_attr_once(ctx, (const void*)fn, &hb_attr[var][gnf ? 1 : 0])) return rc;
   upk_prof_scope prof(ctx, UPK_CLS_IGEMM, stream);
   hipLaunchKernelGGL(fn, dim3(d->m / bm), dim3(512), lds, stream, s);
   return upk_check_launch(ctx, "head_block");

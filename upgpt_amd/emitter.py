@@ -530,17 +530,32 @@ class Emitter:
         P.flops[-1] = 2 * M * (2 * pw1.n_out * C_ + pw2.n_real * (pw1.n_out + C_))
         return out
 
+    def row_chain_rows(self, kind, M, default=32):
+        """Rows per workgroup of a row-chain kernel (kind: "hblock" | "xblock") on an M-row tensor: a forced value
+        (UPGPT_HB_ROWS for the head, UPGPT_XB_ROWS for both), else, with several batches in flight, the decision stored
+        with the shared-chip table ("__row_chain_rows__": {kind: {M: rows}} — 64 workgroups of 128 rows hold a quarter of
+        the chip and stream the weights a quarter as often), else `default`."""
+        forced = (K.HB_ROWS if kind == "hblock" else 0) or K.XB_ROWS
+        if forced:
+            return forced
+        if L.concurrency() > 1 and os.environ.get("UPGPT_LANES_TUNING", "1") == "1":
+            r = TUNE_CACHE_LANES.meta.get("__row_chain_rows__", {}).get(kind, {}).get(str(M))
+            if r:
+                return int(r)
+        return default
+
     def head_block_ok(self, x, t, heads, dp, qk, vt_ld):
         """Whether head_block takes the transformer input x (shape inside the kernel's domain, UPGPT_HBLOCK)."""
         if K.HBLOCK == "0" or (t + ".hblock.vec") not in self.pk.w or x.C % 32:
             return False
-        rows = K.XB_ROWS or 32
+        rows = self.row_chain_rows("hblock", x.M)
         d = L.HblockDesc()
         d.ldx, d.m, d.c, d.heads, d.d = x.C, x.M, x.C, heads, dp
         d.ld_t0, d.ld_qk, d.vt_ld, d.hw, d.rows_per_wg = x.C, qk.ld, vt_ld, x.H * x.W, rows
         if not self.lib.upk_head_block_supported(self.hctx, C.byref(d)):
             return False
-        return K.HBLOCK == "1" or x.M // rows >= self.ctx.num_cus
+        # (the test of "does M cover the chip" is made at 32 rows: the fat forms are chosen to NOT cover it)
+        return K.HBLOCK == "1" or x.M // min(rows, 32) >= self.ctx.num_cus
 
     def head_block(self, P, x, n, t, heads, dp, qk, vt, vt_ld, gn):
         """SpatialTransformer.norm -> proj_in -> norm1 -> q | k | v (include/upk.h upk_head_block_f16); returns t0.
@@ -552,7 +567,7 @@ class Emitter:
         gamma, beta, eps, ws = gn
         M, C_ = x.M, x.C
         hw = x.H * x.W
-        rows = K.XB_ROWS or 32
+        rows = self.row_chain_rows("hblock", M)
         pi, qkv = w[n + ".proj_in"], w[t + ".attn1.qkv_ln"]
         armed = self._arm_gn_sources([x]) if K.HBLOCK_GN else None
         if armed is None:
@@ -628,7 +643,7 @@ class Emitter:
             return None
         M, C_ = t0.M, t0.C
         hw = t0.H * t0.W
-        rows = K.XB_ROWS or (32 if M // 32 >= self.ctx.num_cus else 16)
+        rows = self.row_chain_rows("xblock", M, 32 if M // 32 >= self.ctx.num_cus else 16)
         o1, o2, ql = w[t + ".attn1.to_out"], w[t + ".attn2.to_out"], w[t + ".attn2.q_ln"]
         d = L.XblockDesc()
         d.a1, d.lda, d.m, d.c, d.heads, d.d = a1.t.data_ptr(), a1.ld, M, C_, heads, dp
@@ -640,7 +655,7 @@ class Emitter:
         d.hw, d.rows_per_wg = hw, rows
         if not self.lib.upk_cross_block_supported(self.hctx, C.byref(d)):
             return None
-        if K.XBLOCK == "auto" and M // rows < self.ctx.num_cus:
+        if K.XBLOCK == "auto" and M // min(rows, 32) < self.ctx.num_cus:
             return None  # (every workgroup streams the three weights in full: 16x16 level 34.6 us against 32 us unfused)
         out = Act(self.alloc(M, C_), t0.B, t0.H, t0.W, C_)
         d.y, d.ldy = out.t.data_ptr(), out.ld

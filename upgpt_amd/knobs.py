@@ -23,7 +23,10 @@ MLP_ROWS = int(os.environ.get("UPGPT_MLP_ROWS", "0"))  # rows per workgroup (32 
 # fused cross-attention half of a transformer block (csrc/xblock.hip: attn1.to_out -> norm2 -> to_q -> attention over the
 # context -> attn2.to_out, one launch instead of three / four): "auto", "0" off, "1" wherever the kernel takes the shape
 XBLOCK = os.environ.get("UPGPT_XBLOCK", "auto")
-XB_ROWS = int(os.environ.get("UPGPT_XB_ROWS", "0"))  # rows per workgroup (16 / 32; 0 = by M)
+# rows per workgroup of the row-chain kernels (16 / 32 / 64 / 128; 0 = by M, and with several batches in flight by the
+# "__row_chain_rows__" decision of the shared-chip table): XB_ROWS forces both, HB_ROWS the head alone
+XB_ROWS = int(os.environ.get("UPGPT_XB_ROWS", "0"))
+HB_ROWS = int(os.environ.get("UPGPT_HB_ROWS", "0"))
 # fused head of a SpatialTransformer (csrc/xblock.hip hblock_kernel: proj_in -> norm1 -> q | k | v, one launch instead of two)
 HBLOCK = os.environ.get("UPGPT_HBLOCK", "auto")
 HBLOCK_GN = os.environ.get("UPGPT_HBLOCK_GN", "1") == "1"  # SpatialTransformer.norm applied on the tile inside that launch
