@@ -701,6 +701,57 @@ int upk_style_crops_u8(upk_ctx* ctx, const uint8_t* pictures, long long pic_pitc
                        upk_stream stream);
 
 /* ------------------------------------------------------------------ */
+/* The test split's loader: conditioning maps and stored style crops.    */
+/* ------------------------------------------------------------------ */
+/* The per-pixel work of DeepFashionPair.__getitem__ (deepfashion_inshop.py:173-272) on the bytes PIL decoded.  Every
+ * fp32 result is one correctly rounded IEEE operation at a time in the reference's order: no FMA contraction, no
+ * reciprocal multiply in place of a division.
+ *   src       uint8 maps, byte of pixel (y, x) of sample b at src[b * sample_stride + y * pitch + x] (for the two
+ *             entry points that read pictures: 3 interleaved bytes per pixel, + 3 x + c).  Strides in bytes, any value
+ *             with pitch >= the bytes of a row, no alignment; the sample stride is ignored for batch == 1.
+ *   ytab, xtab   DEVICE int32 [out_h], [out_w]: the source row / column Pillow's NEAREST resize reads for an output row /
+ *             column, built by the caller in double as ImagingScaleAffine does (a = in / out, xo = a * 0.5, per output:
+ *             idx = (int)xo, xo += a; NOT floor((i + 0.5) in / out), which differs at 256 -> 24).  The caller validates
+ *             0 <= idx < in before the upload; upk_cond_gather_u8 clamps an index on the read regardless.
+ *   dst       fp32 dense [batch, 1, out_h, out_w]
+ *
+ * upk_cond_bbox_u8 (input_mask_type 'bbox': get_bbox, then mask_transform): r0 / r1 = the first / last row of a map
+ * holding a non-zero byte, c0 / c1 likewise for columns; boxes[b][4] (DEVICE int32) = r0, r1, c0, c1, or -1, -1, -1, -1
+ * for a map without a non-zero byte.  dst[b][0][y][x] = t(1) when r0 <= ytab[y] <= r1 and c0 <= xtab[x] <= c1, else t(0),
+ * t(u) = fl(fl(u / 255) * 2 - 1): the reference's kept bug of 1 / 255, -0.99215686 inside and -1 outside.  One workgroup
+ * per map: the reduction runs in LDS (integer minima and maxima), then a barrier, then the map's outputs; one launch, no
+ * workspace.  w, pitch, sample stride and src multiples of 16 take 16-byte loads; everything else is read bytewise.
+ *
+ * upk_cond_gather_u8 (input_mask_type 'mask' and loss_w): dst[b][0][y][x] = lut[src[b][ytab[y]][xtab[x]]].
+ *   lut_host  HOST float [256], read during the call and handed to the kernel by value ('mask': lut[u] = t(u); loss_w:
+ *             lut[label] = weight)
+ *
+ * upk_cond_smpl_u8 (input_mask_type 'smpl', after upk_resize_bilinear_u8 made the [h, w] bytes): pictures uint8 HWC ->
+ * dst[b][0][y][x] = fl(fl(fl(fl(r + g) + b) / 3) * 2 - 1) with r, g, b = fl(u / 255): torch.mean(x, 0) * 2. - 1.
+ *
+ * upk_clip_normalize_u8 (clip_transform, deepfashion_inshop.py:128-133, 208-216): n crops uint8 [h][w][3] ->
+ * dst fp32 dense [n, 3, h, w] of fl(fl(fl(u / 255) - mean_c) / std_c), the output stage of upk_style_crops_u8.
+ *   valid     may be NULL: DEVICE int32 [n]; a crop with valid 0 gets the values of u = 0 and its bytes are NOT read (a
+ *             missing style file, the reference's clip_norm(zeros))
+ *   mean_std_host   HOST float [6] = mean[3], std[3] (std > 0)
+ * A workgroup makes 8 rows of one crop.  With w a multiple of 16, 24 w <= 65536 and src, pitch, sample stride and dst
+ * multiples of 16 the rows are staged in LDS by 16-byte loads and every lane writes one 16-byte float4 per plane;
+ * everything else goes per pixel with the same results.
+ * Errors (UPK_EINVAL): a null pointer where none is allowed, non-positive sizes, a pitch below the bytes of a row, std <=
+ * 0, tables / boxes / valid / dst not 4-byte aligned; UPK_ESHAPE: batch (n) > 65535, a map of 2^31 pixels or more.
+ * Nothing is launched on an error.  One launch each, class "other".  Never allocate, never synchronise, graph-capturable. */
+int upk_cond_bbox_u8(upk_ctx* ctx, const uint8_t* src, long long pitch, long long sample_stride, int batch, int h, int w,
+                     const int32_t* ytab, const int32_t* xtab, int out_h, int out_w, float* dst, int32_t* boxes,
+                     upk_stream stream);
+int upk_cond_gather_u8(upk_ctx* ctx, const uint8_t* src, long long pitch, long long sample_stride, int batch, int h, int w,
+                       const int32_t* ytab, const int32_t* xtab, int out_h, int out_w, const float* lut_host, float* dst,
+                       upk_stream stream);
+int upk_cond_smpl_u8(upk_ctx* ctx, const uint8_t* src, long long pitch, long long sample_stride, int batch, int h, int w,
+                     float* dst, upk_stream stream);
+int upk_clip_normalize_u8(upk_ctx* ctx, const uint8_t* src, long long pitch, long long sample_stride, const int32_t* valid,
+                          int n, int h, int w, const float* mean_std_host, float* dst, upk_stream stream);
+
+/* ------------------------------------------------------------------ */
 /* SSIM / MS-SSIM moments of uint8 picture pairs (evaluation metrics).   */
 /* ------------------------------------------------------------------ */
 /* The per-image arithmetic of scripts/eval_metrics.py:110-111 (pytorch_msssim.ssim / ms_ssim with data_range=1,

@@ -27,7 +27,8 @@ SYMBOLS = [
     "upk_nchw_f32_to_nhwc_f16", "upk_nhwc_f16_to_nchw_f32", "upk_f32_to_f16", "upk_ddim_step_f32",
     "upk_ddim_step_cfg_f32", "upk_ddim_step_edit_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
     "upk_patchify_nchw_f32_f16", "upk_vit_assemble_f16", "upk_gather_rows_f16",
-    "upk_image_finish_u8", "upk_resize_bilinear_u8", "upk_segm_boxes_u8", "upk_style_crops_u8", "upk_ssim_ws_bytes", "upk_ssim_u8",
+    "upk_image_finish_u8", "upk_resize_bilinear_u8", "upk_segm_boxes_u8", "upk_style_crops_u8",
+    "upk_cond_bbox_u8", "upk_cond_gather_u8", "upk_cond_smpl_u8", "upk_clip_normalize_u8", "upk_ssim_ws_bytes", "upk_ssim_u8",
     "upk_lpips_input_f16", "upk_relu_pool_nhwc_f16", "upk_lpips_ws_bytes", "upk_lpips_layer_f16",
     "upk_conv2d_rect_f16", "upk_pool3_nhwc_f16", "upk_fid_input_f16", "upk_avgpool_global_f32",
     "upk_advance_step", "upk_step_autoadvance", "upk_kernel_launches", "upk_graph_begin", "upk_graph_end", "upk_graph_launch", "upk_graph_destroy",
@@ -194,6 +195,10 @@ def load_library(path=None):
             "upk_style_crops_u8": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, i32, i32, i32, C.POINTER(C.c_uint32), i32, vp,
                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, C.POINTER(C.c_float), vp, vp, vp,
                                              vp, vp]),
+            "upk_cond_bbox_u8": (C.c_int, [vp, vp, i64, i64, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp]),
+            "upk_cond_gather_u8": (C.c_int, [vp, vp, i64, i64, i32, i32, i32, vp, vp, i32, i32, C.POINTER(C.c_float), vp, vp]),
+            "upk_cond_smpl_u8": (C.c_int, [vp, vp, i64, i64, i32, i32, i32, vp, vp]),
+            "upk_clip_normalize_u8": (C.c_int, [vp, vp, i64, i64, vp, i32, i32, i32, C.POINTER(C.c_float), vp, vp]),
             "upk_ssim_ws_bytes": (C.c_size_t, [i32, i32, i32, i32]),
             "upk_ssim_u8": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, vp, vp, C.c_size_t, vp]),
             "upk_lpips_input_f16": (C.c_int, [vp, vp, i32, i64, i64, i32, i32, i32, i32, C.POINTER(C.c_float), vp, i64, vp]),
@@ -405,6 +410,28 @@ class Context:
                                               int(segm_ss), int(batch), int(h), int(w), lg, int(n_groups), _ptr(boxes), gf, sl,
                                               0 if slot_groups is None else len(slot_groups), ms, _ptr(dst_u8), _ptr(dst_f32),
                                               _ptr(valid), _ptr(coeff_out), self._s()))
+
+    def cond_bbox(self, src, pitch, ss, batch, h, w, ytab, xtab, out_h, out_w, dst, boxes):
+        """upk_cond_bbox_u8: the box of every map's non-zero bytes -> boxes int32 [batch, 4] and the NEAREST-resized box map."""
+        self._chk(self.lib.upk_cond_bbox_u8(self.h, _ptr(src), int(pitch), int(ss), int(batch), int(h), int(w), _ptr(ytab),
+                                            _ptr(xtab), int(out_h), int(out_w), _ptr(dst), _ptr(boxes), self._s()))
+
+    def cond_gather(self, src, pitch, ss, batch, h, w, ytab, xtab, out_h, out_w, lut, dst):
+        """upk_cond_gather_u8; lut: 256 host floats."""
+        lt = None if lut is None else (C.c_float * 256)(*[float(v) for v in lut])
+        self._chk(self.lib.upk_cond_gather_u8(self.h, _ptr(src), int(pitch), int(ss), int(batch), int(h), int(w), _ptr(ytab),
+                                              _ptr(xtab), int(out_h), int(out_w), lt, _ptr(dst), self._s()))
+
+    def cond_smpl(self, src, pitch, ss, batch, h, w, dst):
+        """upk_cond_smpl_u8: uint8 HWC pictures -> fp32 [batch, 1, h, w] of mean(x, 0) * 2 - 1."""
+        self._chk(self.lib.upk_cond_smpl_u8(self.h, _ptr(src), int(pitch), int(ss), int(batch), int(h), int(w), _ptr(dst),
+                                            self._s()))
+
+    def clip_normalize_u8(self, src, pitch, ss, valid, n, h, w, mean_std, dst):
+        """upk_clip_normalize_u8; mean_std: the six host floats mean[3], std[3]; valid: device int32 [n] or None."""
+        ms = None if mean_std is None else (C.c_float * 6)(*[float(v) for v in mean_std])
+        self._chk(self.lib.upk_clip_normalize_u8(self.h, _ptr(src), int(pitch), int(ss), _ptr(valid), int(n), int(h), int(w), ms,
+                                                 _ptr(dst), self._s()))
 
     def ssim_ws_bytes(self, batch, h, w, levels):
         return self.lib.upk_ssim_ws_bytes(int(batch), int(h), int(w), int(levels))

@@ -190,6 +190,13 @@ def run_test(model, batches, save_dir, **log_kwargs):
     return Path(save_dir) / "results"
 
 
+def run_split(model, dataset, save_dir, batch_size=8, **log_kwargs):
+    """run_test over a dataset of this package (upgpt_amd/data.py: DeepFashionPair, the `target` of the model configs'
+    test set): dataset.batches(batch_size) assembles every batch on the device, test_step writes its seven folders.
+    "dataset folder -> results/" with nothing supplied but paths and weights; run_metrics is the step after it."""
+    return run_test(model, dataset.batches(int(batch_size)), save_dir, **log_kwargs)
+
+
 def run_upscale(model, batches, lr_dir, save_dir, pad=(8, 0), **log_kwargs):
     """The second stage of an evaluation run, the flow of the reference's DeepFashionSuperResSampling dataset
     (deepfashion_inshop.py:419-479) through the upscale model: for every batch dict (`fname`, `styles`, `txt`, `image`)
