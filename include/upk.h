@@ -927,6 +927,61 @@ int upk_fid_input_f16(upk_ctx* ctx, const void* src, int src_f32, long long pitc
 int upk_avgpool_global_f32(upk_ctx* ctx, const void* x, int ld, int n, int hw, int c, float* out, upk_stream stream);
 
 /* ------------------------------------------------------------------ */
+/* The denoising loss: q_sample and p_losses (validation).                */
+/* ------------------------------------------------------------------ */
+/* What LatentDiffusion.p_losses (ddpm.py:1083-1123) does around its one UNet forward.  Both entry points never allocate,
+ * never synchronise, are graph-capturable, and count their launches in class "other".
+ *
+ * upk_q_sample_f32: q_sample (ddpm.py:271-274) with one timestep per sample, one launch.
+ *   x_start, noise   fp32 NCHW [batch, c, hw], dense
+ *   t                int32 [batch]; a, s = sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod: fp32 tables of n_t entries
+ *   x_noisy          fp32 NCHW [batch, c, hw], or NULL
+ *   xin              the UNet stem input, fp16 NHWC [batch * hw, ld_xin], or NULL: channels [0, c) of every row are written,
+ *                    as upk_ddim_step_f32 writes them; channels >= c of a row are left untouched
+ * v = fl(fl(a[t_b] * x0) + fl(s[t_b] * n)): three correctly rounded IEEE fp32 operations, no FMA contraction, bit for bit
+ * what torch's fp32 expression gives on the CPU; x_noisy = v, xin = v rounded once to fp16 (to nearest even).  A t_b outside
+ * [0, n_t) is never used as an index: every output of that sample is NaN, the other samples are as without it.  With x_start,
+ * noise and x_noisy 16-byte aligned a thread moves 4 consecutive elements with 16-byte loads and stores (a group may cross
+ * a channel or a sample) and the batch * c * hw % 4 last elements go one per thread; otherwise every element goes alone.
+ * Errors: UPK_EINVAL for null inputs, x_noisy and xin both NULL, non-positive sizes, ld_xin < c, an fp32 / int32 pointer not
+ * 4-byte or xin not 2-byte aligned; UPK_ESHAPE for c * hw above 2^31 - 1 - 8192 or more than 2^31 - 1 workgroups. */
+int upk_q_sample_f32(upk_ctx* ctx, const float* x_start, const float* noise, const int32_t* t,
+                     const float* sqrt_alphas_cumprod, const float* sqrt_one_minus_alphas_cumprod, int n_t, float* x_noisy,
+                     void* xin, int ld_xin, int batch, int c, int hw, upk_stream stream);
+/* upk_p_losses_f32: the loss values of ddpm.py:1101-1121 from model_out and target, fp32 [batch, c, hw] dense.
+ *   loss_w           fp32 [batch, loss_w_channels, hw] with loss_w_channels 1 (broadcast over c) or c; NULL: no weighting
+ *   t                int32 [batch]; logvar, lvlb_weights: fp32 tables of n_t entries
+ *   loss_type        UPK_LOSS_L2: e = (target - pred)^2; UPK_LOSS_L1: e = |target - pred|
+ *   per element      d = fl(target - pred), e = fl(d * d) or |d|, we = fl(w * e) (we = e without loss_w): fp32, one IEEE
+ *                    operation at a time, as the reference forms them
+ *   per sample b     simple[b] = mean over (c, hw) of we, plain[b] = mean over (c, hw) of e
+ *   batch            loss_simple = mean_b simple[b];  loss_gamma = mean_b (simple[b] / exp(logvar[t_b]) + logvar[t_b]);
+ *                    loss_vlb = mean_b (lvlb_weights[t_b] * plain[b]);
+ *                    loss = l_simple_weight * loss_gamma + original_elbo_weight * loss_vlb
+ *   out              fp32 [4 + 2 batch]: {loss, loss_simple, loss_gamma, loss_vlb}, then {simple[b], plain[b]} per sample
+ *   ws               upk_p_losses_ws_bytes(batch, c, hw) bytes (0 for sizes upk_p_losses_f32 would refuse), 16-byte aligned:
+ *                    one slot of two fp64 partial sums per workgroup
+ * Every fp32 term is widened to fp64 when it is made, and everything after it (the sums, the means, exp, the batch terms)
+ * is fp64, rounded once to fp32 on output: simple, plain, loss_simple and loss_vlb are within relative 4 * 2^-24 of the exact
+ * value for the given fp32 inputs (three roundings per non-negative term, one at the output), loss_gamma and loss within
+ * 4 * 2^-24 of the sum of the magnitudes of their terms.  Deterministic like upk_ssim_u8: no float atomics; every workgroup
+ * (one sample's chunk of 4096 elements) writes its own slot and a fixed-order pass sums them, so reruns are bit-identical
+ * and simple[b], plain[b] depend neither on the sample's position in the batch nor on the batch size, nor on whether the
+ * 16-byte loads were used (hw % 4 == 0 and model_out, target, loss_w 16-byte aligned; one element per load otherwise).
+ * A t_b outside [0, n_t) is never used as an index: simple[b], plain[b] and with them the four batch values are NaN.
+ * Errors: UPK_EINVAL for null pointers (loss_w excepted), non-positive sizes, another loss_type, loss_w with a channel count
+ * other than 1 or c, an fp32 / int32 pointer not 4-byte or ws not 16-byte aligned; UPK_ESHAPE for c * hw above 2^31 - 1 -
+ * 8192 or more than 2^31 - 1 workgroups; UPK_EWORKSPACE for ws_bytes below upk_p_losses_ws_bytes.  Two launches (partial
+ * sums, final pass). */
+#define UPK_LOSS_L2 0
+#define UPK_LOSS_L1 1
+size_t upk_p_losses_ws_bytes(int batch, int c, int hw);
+int upk_p_losses_f32(upk_ctx* ctx, const float* model_out, const float* target, const float* loss_w, int loss_w_channels,
+                     const int32_t* t, const float* logvar, const float* lvlb_weights, int n_t, int loss_type,
+                     float l_simple_weight, float original_elbo_weight, float* out, int batch, int c, int hw, void* ws,
+                     size_t ws_bytes, upk_stream stream);
+
+/* ------------------------------------------------------------------ */
 /* CU-partitioned streams (execution lanes on disjoint CU sets).         */
 /* The reference has no counterpart: it runs one batch on `cuda:0`       */
 /* (app.py:21); lanes are this build's serving mode. */

@@ -31,6 +31,7 @@ SYMBOLS = [
     "upk_cond_bbox_u8", "upk_cond_gather_u8", "upk_cond_smpl_u8", "upk_clip_normalize_u8", "upk_ssim_ws_bytes", "upk_ssim_u8",
     "upk_lpips_input_f16", "upk_relu_pool_nhwc_f16", "upk_lpips_ws_bytes", "upk_lpips_layer_f16",
     "upk_conv2d_rect_f16", "upk_pool3_nhwc_f16", "upk_fid_input_f16", "upk_avgpool_global_f32",
+    "upk_q_sample_f32", "upk_p_losses_ws_bytes", "upk_p_losses_f32",
     "upk_advance_step", "upk_step_autoadvance", "upk_kernel_launches", "upk_graph_begin", "upk_graph_end", "upk_graph_launch", "upk_graph_destroy",
     "upk_prof_enable", "upk_prof_collect",
     "upk_stream_create_cumask", "upk_stream_destroy", "upk_probe_placement", "upk_probe_clock",
@@ -43,6 +44,7 @@ STYLE_FILL, STYLE_MASK = 0x1, 0x2  # upk_style_crops_u8 group flags (max_rows <<
 FINISH_SAMPLE, FINISH_INPUT, FINISH_DENORM = 0, 1, 2  # ... and arithmetic modes
 F_QUICKGELU = 0x40
 POOL_MAX, POOL_AVG = 0, 1  # upk_pool3_nhwc_f16 modes
+LOSS_L2, LOSS_L1 = 0, 1  # upk_p_losses_f32 loss types
 NUM_CLASSES = 5
 CLASS_NAMES = ["igemm", "attention", "groupnorm", "layernorm", "other"]
 
@@ -210,6 +212,10 @@ def load_library(path=None):
             "upk_pool3_nhwc_f16": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
             "upk_fid_input_f16": (C.c_int, [vp, vp, i32, i64, i64, i32, i32, i32, i32, i32, i32, vp, i64, vp]),
             "upk_avgpool_global_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, vp]),
+            "upk_q_sample_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp]),
+            "upk_p_losses_ws_bytes": (C.c_size_t, [i32, i32, i32]),
+            "upk_p_losses_f32": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32, vp, i32, i32, i32, vp,
+                                           C.c_size_t, vp]),
             "upk_advance_step": (C.c_int, [vp, vp, vp]),
             "upk_step_autoadvance": (C.c_int, [vp, vp]),
             "upk_kernel_launches": (C.c_longlong, [vp, i32]),
@@ -481,6 +487,23 @@ class Context:
     def avgpool_global(self, x, ld, n, hw, c, out):
         """upk_avgpool_global_f32: fp16 [n, hw, ld] -> fp32 [n, c] means."""
         self._chk(self.lib.upk_avgpool_global_f32(self.h, _ptr(x), int(ld), int(n), int(hw), int(c), _ptr(out), self._s()))
+
+    def q_sample(self, x_start, noise, t, sqrt_ac, sqrt_1m_ac, n_t, x_noisy, xin, ld_xin, batch, c, hw):
+        """upk_q_sample_f32: x_noisy (fp32 NCHW) and / or channels [0, c) of xin (fp16 NHWC) <- a[t] * x_start + s[t] * noise."""
+        self._chk(self.lib.upk_q_sample_f32(self.h, _ptr(x_start), _ptr(noise), _ptr(t), _ptr(sqrt_ac), _ptr(sqrt_1m_ac),
+                                            int(n_t), _ptr(x_noisy), _ptr(xin), int(ld_xin), int(batch), int(c), int(hw),
+                                            self._s()))
+
+    def p_losses_ws_bytes(self, batch, c, hw):
+        return self.lib.upk_p_losses_ws_bytes(int(batch), int(c), int(hw))
+
+    def p_losses(self, model_out, target, loss_w, loss_w_channels, t, logvar, lvlb_weights, n_t, loss_type, l_simple_weight,
+                 original_elbo_weight, out, batch, c, hw, ws, ws_bytes):
+        """upk_p_losses_f32: out [4 + 2 batch] fp32 = {loss, loss_simple, loss_gamma, loss_vlb}, then {simple, plain} per sample."""
+        self._chk(self.lib.upk_p_losses_f32(self.h, _ptr(model_out), _ptr(target), _ptr(loss_w), int(loss_w_channels), _ptr(t),
+                                            _ptr(logvar), _ptr(lvlb_weights), int(n_t), int(loss_type), float(l_simple_weight),
+                                            float(original_elbo_weight), _ptr(out), int(batch), int(c), int(hw), _ptr(ws),
+                                            int(ws_bytes), self._s()))
 
     def step_autoadvance(self, done):
         """Arms (done: zeroed device int32) or disarms (None) the step kernels' own increment of *step."""

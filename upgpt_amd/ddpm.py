@@ -1,15 +1,20 @@
-"""DDPM / LatentDiffusion / DiffusionWrapper — the inference call surface of
+"""DDPM / LatentDiffusion / DiffusionWrapper — the inference and validation call surface of
 ldm/models/diffusion/ddpm.py.
 
 What is CONTRACT here (and therefore kept name for name): the constructor keyword arguments, so that the `model:`
 block of configs/deepfashion/bbox.yaml instantiates unchanged; the module / buffer names that make reference
 checkpoints load (model.diffusion_model.*, model_ema.*, first_stage_model.*, cond_stage_model.*, extra_cond_models.*,
 the schedule buffers); the methods the named callers use (apply_model, decode_first_stage, get_learned_conditioning,
-ema_scope, q_sample, sample_log, log_images, test_step, get_input) with their argument order and return shapes.  Everything
-else is this package's own: the schedule buffers come out of one table, conditioning assembly lives in one place
-(`_conditioning`), EMA evaluation packs the shadow weights instead of copying them over the live ones, and the
-training-side state of the reference (loss weights, log-variance, ELBO terms, LR scheduler config) does not exist —
-those keyword arguments are accepted and ignored, the training entry points raise.
+ema_scope, q_sample, sample_log, log_images, test_step, get_input, get_loss, p_losses, forward, shared_step,
+validation_step) with their argument order and return shapes.  Everything else is this package's own: the schedule
+buffers come out of one table, conditioning assembly lives in one place (`_conditioning`), EMA evaluation packs the
+shadow weights instead of copying them over the live ones.
+
+The LOSS side exists as far as evaluating it goes: loss_type, l_simple_weight, original_elbo_weight,
+learn_logvar and logvar_init are honoured, `lvlb_weights` and `logvar` exist as in the reference, and p_losses / forward /
+shared_step / validation_step compute the reference's loss_dict — forward only, through upk_q_sample_f32 and
+upk_p_losses_f32 around the UNet forward.  There is no backward pass, no optimizer and no EMA update: training_step and
+configure_optimizers raise, scheduler_config is accepted and ignored.
 
 Plain torch.nn.Modules (no pytorch_lightning); every FLOP of the denoiser / first stage runs in the HIP engine.
 """
@@ -27,6 +32,7 @@ from .ema import LitEma
 from .grid import make_grid
 from .schedule import extract_into_tensor, make_beta_schedule
 from .vae import AutoencoderKL
+from . import _lib
 from ._check import require
 
 
@@ -115,9 +121,10 @@ class DDPM(nn.Module):
             raise AssertionError('currently only supporting "eps" and "x0"')
         if v_posterior:
             raise NotImplementedError("v_posterior != 0 changes the posterior variance buffers; not used by UPGPT")
-        # loss_type, monitor, log_every_t, original_elbo_weight, l_simple_weight, scheduler_config, learn_logvar and
-        # logvar_init configure the training loop of the reference and do nothing here; the plain attributes its
-        # scripts read (main.py:653 model.monitor, classifier.py:204 diffusion_model.log_every_t) are kept
+        # loss_type, original_elbo_weight, l_simple_weight, learn_logvar and logvar_init shape the loss values of
+        # p_losses / validation_step; scheduler_config configures the training loop of the reference and does nothing
+        # here; monitor and log_every_t are the plain attributes its scripts read (main.py:653 model.monitor,
+        # classifier.py:204 diffusion_model.log_every_t)
         self.loss_type, self.monitor, self.log_every_t = loss_type, monitor, log_every_t
         self.v_posterior, self.original_elbo_weight, self.l_simple_weight = v_posterior, original_elbo_weight, l_simple_weight
         self.use_scheduler, self.learn_logvar = scheduler_config is not None, learn_logvar
@@ -135,6 +142,10 @@ class DDPM(nn.Module):
             self.model_ema = LitEma(denoiser)  # shadow buffers `model_ema.*` of the checkpoints
             print(f"Keeping EMAs of {sum(1 for _ in self.model_ema.buffers())}.")
         self.register_schedule(given_betas, beta_schedule, timesteps, linear_start, linear_end, cosine_s)
+        # (ddpm.py:120-122) a checkpoint key only when it is learned; a plain CPU tensor otherwise, as in the reference
+        self.logvar = torch.full(fill_value=float(logvar_init), size=(self.num_timesteps,))
+        if self.learn_logvar:
+            self.logvar = nn.Parameter(self.logvar, requires_grad=True)
         if ckpt_path is not None and type(self) is DDPM:
             self.init_from_ckpt(ckpt_path, ignore_keys, only_model=load_only_unet)
 
@@ -153,6 +164,17 @@ class DDPM(nn.Module):
         self.linear_start, self.linear_end = linear_start, linear_end
         for name, fn in _SCHEDULE:
             self.register_buffer(name, torch.tensor(fn(betas, acp, acp_prev), dtype=torch.float32))
+        # (ddpm.py:167-176) the weights of the variational-bound term, formed from the fp32 BUFFERS in fp32, in the
+        # reference's operation order, not in float64; entry 0 (posterior_variance[0] = 0: a division by zero) is
+        # replaced by entry 1
+        if self.parameterization == "eps":
+            alphas = torch.tensor(1.0 - betas, dtype=torch.float32)
+            lvlb = self.betas ** 2 / (2 * self.posterior_variance * alphas * (1 - self.alphas_cumprod))
+        else:
+            lvlb = 0.5 * torch.sqrt(self.alphas_cumprod) / (2. * 1 - self.alphas_cumprod)
+        lvlb[0] = lvlb[1]
+        self.register_buffer("lvlb_weights", lvlb, persistent=False)
+        require(not torch.isnan(self.lvlb_weights).all(), "lvlb_weights are all NaN", AssertionError)
 
     @contextmanager
     def ema_scope(self, context=None):
@@ -201,10 +223,41 @@ class DDPM(nn.Module):
             x = x.unsqueeze(-1)
         return x.movedim(-1, 1).contiguous().float()
 
-    def training_step(self, *a, **k):
-        raise NotImplementedError("training is out of scope of upgpt_amd (inference hot path only)")
+    def get_loss(self, pred, target, mean=True):
+        """ddpm.py:276-290: |target - pred| (l1) or (target - pred)^2 (l2), per element or its mean.  Plain tensor
+        arithmetic on whatever device the arguments are on; p_losses does not call it (upk_p_losses_f32 forms the
+        same terms)."""
+        if self.loss_type == "l1":
+            loss = (target - pred).abs()
+        elif self.loss_type == "l2":
+            loss = (target - pred) ** 2
+        else:
+            raise NotImplementedError("unknown loss type '%s'" % (self.loss_type,))
+        return loss.mean() if mean else loss
 
-    p_losses = configure_optimizers = validation_step = training_step
+    def _logvar_table(self, dev):
+        """logvar as an fp32 table on `dev`: the Parameter itself when it lives there, else a copy made once per
+        (device, version) — the plain tensor stays on the host when the module moves, as in the reference."""
+        lv = self.logvar
+        if lv.device == dev and lv.dtype == torch.float32:
+            return lv.detach()
+        key = (dev, lv._version, lv.data_ptr())
+        ent = self.__dict__.get("_logvar_dev")
+        if ent is None or ent[0] != key:
+            ent = self.__dict__["_logvar_dev"] = (key, lv.detach().to(dev, torch.float32))
+        return ent[1]
+
+    def training_step(self, *a, **k):
+        raise NotImplementedError("training is out of scope of upgpt_amd: the loss is evaluated (p_losses, "
+                                  "validation_step), there is no backward pass and no optimizer")
+
+    configure_optimizers = training_step
+
+    def p_losses(self, *a, **k):
+        raise NotImplementedError("DDPM.p_losses without conditioning: the UNet here requires a context "
+                                  "(LatentDiffusion.p_losses)")
+
+    validation_step = p_losses
 
 
 class LatentDiffusion(AncestralSampling, DDPM):
@@ -402,6 +455,103 @@ class LatentDiffusion(AncestralSampling, DDPM):
             out.append(batch.get("loss_w", None))
         return out
 
+    # ---- the validation loss
+    @torch.no_grad()
+    def p_losses(self, x_start, cond, t, noise=None, loss_w=None):
+        """ddpm.py:1083-1123 -> (loss, loss_dict), forward only.  loss_dict has the reference's keys under its prefix
+        ('train' if self.training else 'val'): <prefix>/loss_simple, <prefix>/loss_vlb, <prefix>/loss, and with
+        learn_logvar also <prefix>/loss_gamma and 'logvar'; the values are 0-dim fp32 device tensors.
+        x_start [B, C, H, W]; t [B] integer timesteps; noise defaults to randn_like(x_start) on the device; loss_w is
+        None, [B, 1, H, W] (what the loader makes) or [B, C, H, W].  Target: noise ('eps') or x_start ('x0').
+        Path: upk_q_sample_f32 writes a_t x0 + s_t noise straight into the forward plan's stem input (fp16 NHWC, no
+        fp32 x_noisy is kept), the plan's loader puts the concat channels behind it, the UNet runs with one timestep
+        per sample, and upk_p_losses_f32 reduces its fp32 output against the target (fixed-order fp64 sums, no
+        atomics): three launches around the forward and no host synchronisation.  self.loss_terms keeps the kernel's
+        whole output of the last call: {loss, loss_simple, loss_gamma, loss_vlb}, then {simple, plain} per sample.
+        NOT reproduced: the reference's `image = self.decode_first_stage(model_output)` (its line 1089) decodes the
+        model output to a picture and drops it; nothing is decoded here."""
+        unet = self.model.diffusion_model
+        dev = unet._device()  # (RuntimeError on a CPU model: there is no CPU fallback)
+        require(x_start.dim() == 4 and t.shape[0] == x_start.shape[0], "p_losses: x_start [B, C, H, W] and t [B]", ValueError)
+        require(self.loss_type in ("l1", "l2"), "unknown loss type '%s'" % (self.loss_type,), NotImplementedError)
+        B, C, H, W = x_start.shape
+        cc, ca = self._split_cond(cond)
+        ncat = 0 if cc is None else cc.shape[1]
+        require(C + ncat == unet.in_channels and C == unet.out_channels, lambda: "latent %d + concat %d channels against "
+                "a UNet of %d in, %d out" % (C, ncat, unet.in_channels, unet.out_channels), ValueError)
+        pl = unet.plan(B, H, W, ca.shape[1], B, "forward")
+        ctx, n_t = pl.ctx, self.num_timesteps
+        with torch.cuda.device(dev):
+            x_start = x_start.to(dev, torch.float32).contiguous()
+            noise = torch.randn_like(x_start) if noise is None else noise.to(dev, torch.float32).contiguous()
+            require(noise.shape == x_start.shape, "p_losses: noise and x_start differ in shape", ValueError)
+            t32 = t.to(dev, torch.int32).contiguous()
+            wc = 0
+            if loss_w is not None:
+                wc = 1 if loss_w.dim() == 4 and loss_w.shape[1] == 1 else C
+                loss_w = loss_w.to(dev, torch.float32).expand(B, wc, H, W).contiguous()
+            ctx.q_sample(x_start, noise, t32, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, n_t, None,
+                         pl.xin.t, pl.xin.ld, B, C, H * W)
+            if cc is not None:
+                pl.load_x_nchw(cc, C, pl.cin_pad)
+            pl.t_rows.copy_(t32)
+            pl._t_rows_key = None  # (a sampler sharing this plan re-uploads its rows)
+            pl.load_context(ca)
+            pl.prep.run()
+            pl.body.run()
+            target = noise if self.parameterization == "eps" else x_start
+            nbytes = ctx.p_losses_ws_bytes(B, C, H * W)
+            require(nbytes > 0, "upk_p_losses_ws_bytes refused (%d, %d, %d)" % (B, C, H * W), RuntimeError)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            out = torch.empty(4 + 2 * B, dtype=torch.float32, device=dev)
+            logvar = self._logvar_table(dev)
+            ctx.p_losses(pl.eps, target, loss_w, wc, t32, logvar, self.lvlb_weights, n_t,
+                         _lib.LOSS_L1 if self.loss_type == "l1" else _lib.LOSS_L2, self.l_simple_weight,
+                         self.original_elbo_weight, out, B, C, H * W, ws, nbytes)
+            prefix = "train" if self.training else "val"
+            loss_dict = {prefix + "/loss_simple": out[1]}
+            if self.learn_logvar:
+                loss_dict[prefix + "/loss_gamma"] = out[2]
+                loss_dict["logvar"] = logvar.mean()
+            loss_dict[prefix + "/loss_vlb"] = out[3]
+            loss_dict[prefix + "/loss"] = out[0]
+            self.__dict__["loss_terms"] = out  # (the kernel's whole output of the last call, for diagnostics)
+        return out[0], loss_dict
+
+    def forward(self, x, c, *args, **kwargs):
+        """ddpm.py:941-950: one uniformly drawn timestep per sample (on the device), then p_losses."""
+        t = torch.randint(0, self.num_timesteps, (x.shape[0],), device=self.device).long()
+        if self.model.conditioning_key is not None:
+            require(c is not None, "a conditional model needs its conditioning", AssertionError)
+        return self.p_losses(x, c, t, *args, **kwargs)
+
+    def shared_step(self, batch, **kwargs):
+        """ddpm.py:931-939."""
+        x, c, w = self.get_input(batch, self.first_stage_key, return_loss_w=True)
+        return self(x, c, loss_w=w)
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx=0):
+        """ddpm.py:364-371: the loss_dict of the live weights and, under the suffix '_ema', of the EMA weights (inside
+        ema_scope()).  The reference hands both to Lightning's log_dict (on_epoch means); here the merged dict is
+        RETURNED (evaluate.run_validation forms the epoch means) and also passed to self.log_dict when the instance
+        has one.  The encoder moments and the conditioning are computed once and shared by the two passes; each pass
+        draws its own posterior sample, timesteps and noise, in the reference's order (live first)."""
+        dev = self.model.diffusion_model._device()
+        x = DDPM.get_input(self, batch, self.first_stage_key).to(dev)
+        posterior = self.encode_first_stage(x)
+        _, c, w = self.get_input(batch, self.first_stage_key, return_loss_w=True, encode_image=False)
+        _, merged = self(self.get_first_stage_encoding(posterior).detach(), c, loss_w=w)
+        with self.ema_scope():
+            _, ema = self(self.get_first_stage_encoding(posterior).detach(), c, loss_w=w)
+        merged = dict(merged)
+        merged.update({k + "_ema": v for k, v in ema.items()})
+        log_dict = getattr(self, "log_dict", None)
+        if callable(log_dict):
+            log_dict(merged, prog_bar=False, logger=True, on_step=False, on_epoch=True)
+        return merged
+
+    # ---- sampling / logging (continued)
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
         """ddpm.py:1312-1325."""

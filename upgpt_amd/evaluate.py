@@ -197,6 +197,44 @@ def run_split(model, dataset, save_dir, batch_size=8, **log_kwargs):
     return run_test(model, dataset.batches(int(batch_size)), save_dir, **log_kwargs)
 
 
+def run_validation(model, dataset, batch_size=8, seed=0, max_batches=None, save_dir=None):
+    """The validation epoch of trainer.validate without Lightning: dataset.batches(batch_size) (upgpt_amd/data.py; any
+    object with that method, or a plain iterable of batch dicts) through model.validation_step, and the epoch means of
+    its keys as Lightning's on_epoch reduction forms them — every batch's value weighted by the batch's size — as a plain
+    {key: float} dict, e.g. 'val/loss_simple_ema', the number the UPGPT configs monitor.  With save_dir they are also
+    written to <save_dir>/val_metrics.json.
+    The timesteps, the noise and the posterior samples come from the device generator, seeded with `seed` for the
+    duration (the generators' states are put back afterwards), so a run is repeatable.  The values stay on the device:
+    they are accumulated there in fp64 and cross to the host in one copy behind the run's only synchronise."""
+    import json
+    dev = model.model.diffusion_model._device()
+    batches = dataset.batches(int(batch_size)) if hasattr(dataset, "batches") else dataset
+    keys, acc, count = None, None, 0
+    with torch.cuda.device(dev), torch.random.fork_rng(devices=[dev.index]):
+        torch.manual_seed(int(seed))
+        for i, batch in enumerate(batches):
+            if max_batches is not None and i >= int(max_batches):
+                break
+            n = int(batch[model.first_stage_key].shape[0])
+            d = model.validation_step(batch, i)
+            if keys is None:
+                keys = list(d)
+                acc = torch.zeros(len(keys), dtype=torch.float64, device=dev)
+            require(list(d) == keys, "validation_step returned other keys than for the first batch", RuntimeError)
+            acc += torch.stack([d[k].reshape(()) for k in keys]).double() * n
+            count += n
+        require(count > 0, "run_validation: no batches", ValueError)
+        host = torch.empty(len(keys), dtype=torch.float64, pin_memory=True)
+        host.copy_(acc / count, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+    means = {k: float(v) for k, v in zip(keys, host.tolist())}
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+        with open(os.path.join(str(save_dir), "val_metrics.json"), "w") as f:
+            json.dump(means, f, indent=1)
+    return means
+
+
 def run_upscale(model, batches, lr_dir, save_dir, pad=(8, 0), **log_kwargs):
     """The second stage of an evaluation run, the flow of the reference's DeepFashionSuperResSampling dataset
     (deepfashion_inshop.py:419-479) through the upscale model: for every batch dict (`fname`, `styles`, `txt`, `image`)
