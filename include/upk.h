@@ -392,6 +392,24 @@ int upk_attention_qproj_f16(upk_ctx* ctx, const void* x, int ldx, long long xbs,
                             long long kbs, const void* vt, int vt_ld, void* out, int ldo, long long obs, int batch,
                             int heads, int n_q, int n_kv, int d, float scale, upk_stream stream);
 
+/* Attention over a HANDFUL of keys: out = softmax(Q K^T * scale) V with 1 <= n_kv <= 16 — the cross-attention of
+ * CLIPTextImageCrossAtten (ldm/modules/encoders/modules.py:259-323: 77 text tokens over 9 style embeddings, 8 heads
+ * of 96).  q / out as upk_attention_f16; k and v: fp16 [B, n_kv, ldk] / [B, n_kv, ldv] in the NATURAL layout (head h
+ * at columns [h*d, (h+1)*d), not transposed, no key padding), so they may be two column slices of one k|v GEMM output.
+ * 8 <= d <= 128 with d % 8 == 0 (no head padding), n_q >= 1; every leading dimension a multiple of 8 and
+ * >= heads * d; pointers and batch strides 16-byte aligned.  Anything else: UPK_ESHAPE, nothing is launched.
+ * VALU kernel, one lane per query: fp32 scores, max-subtracted fp32 softmax, fp32 P V, fp16 output; columns of out
+ * beyond heads * d are not written. */
+int upk_attention_fewkeys_f16(upk_ctx* ctx, const void* q, int ldq, long long q_batch_stride, const void* k, int ldk,
+                              long long k_batch_stride, const void* v, int ldv, long long v_batch_stride, void* out,
+                              int ldo, long long o_batch_stride, int batch, int heads, int n_q, int n_kv, int d,
+                              float scale, upk_stream stream);
+
+/* x <- 0.5 x (1 + erf(x / sqrt 2)) in place over fp16 [rows, cols], rows ld apart: the activation of a CLIP MLP whose
+ * hidden_act is "gelu" (laion CLIP), behind a plain fc1 GEMM.  fp32 math by the device function of the GEGLU
+ * epilogues (the two agree bit for bit).  cols and ld multiples of 8, ld >= cols, x 16-byte aligned; else UPK_ESHAPE. */
+int upk_gelu_f16(upk_ctx* ctx, void* x, int ld, int rows, int cols, upk_stream stream);
+
 /* out[r, :] = tok_emb[ids[r], :] + pos_emb[r % seq, :]  (fp16 tables [vocab, dim] / [seq, dim], fp16 out [rows, ld]):
  * CLIPTextEmbeddings.  ids outside [0, vocab) are an error the kernel cannot report: validate on the host. */
 int upk_embed_tokens_f16(upk_ctx* ctx, const int32_t* ids, const void* tok_emb, const void* pos_emb, int rows,

@@ -26,6 +26,7 @@ SYMBOLS = [
     "upk_layernorm_f16", "upk_timestep_embed_f16",
     "upk_nchw_f32_to_nhwc_f16", "upk_nhwc_f16_to_nchw_f32", "upk_f32_to_f16", "upk_ddim_step_f32",
     "upk_ddim_step_cfg_f32", "upk_ddim_step_edit_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
+    "upk_attention_fewkeys_f16", "upk_gelu_f16",
     "upk_patchify_nchw_f32_f16", "upk_vit_assemble_f16", "upk_gather_rows_f16",
     "upk_image_finish_u8", "upk_resize_bilinear_u8", "upk_segm_boxes_u8", "upk_style_crops_u8",
     "upk_cond_bbox_u8", "upk_cond_gather_u8", "upk_cond_smpl_u8", "upk_clip_normalize_u8", "upk_ssim_ws_bytes", "upk_ssim_u8",
@@ -165,6 +166,9 @@ def load_library(path=None):
                                                    i32, i32, i32, i32, f32, vp]),
             "upk_attention_qproj_f16": (C.c_int, [vp, vp, i32, i64, i32, i32, f32, vp, vp, vp, vp, i32, i64, vp, i32, vp,
                                                   i32, i64, i32, i32, i32, i32, i32, f32, vp]),
+            "upk_attention_fewkeys_f16": (C.c_int, [vp, vp, i32, i64, vp, i32, i64, vp, i32, i64, vp, i32, i64,
+                                                    i32, i32, i32, i32, i32, f32, vp]),
+            "upk_gelu_f16": (C.c_int, [vp, vp, i32, i32, i32, vp]),
             "upk_embed_tokens_f16": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp]),
             "upk_gather_rows_f16": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, vp, i32, vp]),
             "upk_patchify_nchw_f32_f16": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp]),
@@ -313,6 +317,17 @@ class Context:
     def attention_causal(self, q, ldq, qbs, k, ldk, kbs, vt, vt_ld, out, ldo, obs, batch, heads, n, d, scale):
         self._chk(self.lib.upk_attention_causal_f16(self.h, _ptr(q), ldq, qbs, _ptr(k), ldk, kbs, _ptr(vt), vt_ld,
                                                     _ptr(out), ldo, obs, batch, heads, n, d, scale, self._s()))
+
+    def attention_fewkeys(self, q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, out, ldo, obs, batch, heads, n_q, n_kv, d, scale):
+        """upk_attention_fewkeys_f16: 1 <= n_kv <= 16 keys, k / v in the natural [B, n_kv, ld] layout (column slices of one
+        k|v GEMM output), 8 <= d <= 128 with d % 8 == 0."""
+        self._chk(self.lib.upk_attention_fewkeys_f16(self.h, _ptr(q), int(ldq), int(qbs), _ptr(k), int(ldk), int(kbs),
+                                                     _ptr(v), int(ldv), int(vbs), _ptr(out), int(ldo), int(obs), int(batch),
+                                                     int(heads), int(n_q), int(n_kv), int(d), float(scale), self._s()))
+
+    def gelu(self, x, ld, rows, cols):
+        """upk_gelu_f16: exact (erf) GELU in place over fp16 [rows, cols], rows ld apart."""
+        self._chk(self.lib.upk_gelu_f16(self.h, _ptr(x), int(ld), int(rows), int(cols), self._s()))
 
     def embed_tokens(self, ids, tok, pos, rows, seq, dim, vocab, out, ld):
         self._chk(self.lib.upk_embed_tokens_f16(self.h, _ptr(ids), _ptr(tok), _ptr(pos), rows, seq, dim, vocab, _ptr(out),

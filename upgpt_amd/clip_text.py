@@ -32,7 +32,17 @@ from .params import ParamTree, weights_fingerprint
 
 # openai/clip-vit-large-patch14 text tower (config.json of the hub model; CLIPTextConfig)
 CLIP_L14_TEXT = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12,
-                     num_attention_heads=12, max_position_embeddings=77, layer_norm_eps=1e-5)
+                     num_attention_heads=12, max_position_embeddings=77, layer_norm_eps=1e-5, hidden_act="quick_gelu")
+# hidden_act: "quick_gelu" (OpenAI's towers: x * sigmoid(1.702 x), a GEMM epilogue) or "gelu" (the laion towers: exact erf
+# GELU, upk_gelu_f16 behind a plain fc1 launch)
+HIDDEN_ACTS = ("quick_gelu", "gelu")
+
+
+def hidden_act(cfg):
+    act = cfg.get("hidden_act", "quick_gelu")
+    if act not in HIDDEN_ACTS:
+        raise NotImplementedError("CLIP tower with hidden_act %r (known: %s)" % (act, ", ".join(HIDDEN_ACTS)))
+    return act
 
 
 def text_param_shapes(cfg):
@@ -100,6 +110,7 @@ class _TextPlan(Emitter):
         if dh not in (32, 64, 128) or d % 32 or f % 32:
             raise NotImplementedError("CLIP text tower with head dim %d / width %d" % (dh, d))
         eps = float(cfg["layer_norm_eps"])
+        erf_gelu = hidden_act(cfg) == "gelu"
         pk = Packer(ctx, get)
         if shared is not None:  # (one packed tower for every lane's plan)
             pk = shared.wrap(pk)
@@ -129,7 +140,10 @@ class _TextPlan(Emitter):
             P.add(lambda s, aa=aa: chk(fn_a(h, *aa, s)), qk, vt, att, cls="attention")
             x = self.conv(P, att, pk.pack(p + nm["out"]), residual=x)
             # second LayerNorm folded into the first MLP GEMM; quick_gelu in its epilogue; the second adds the residual
-            hmid = self.conv(P, x, pk.pack(p + nm["fc1"], ln=p + nm["ln2"]), ln_eps=eps, flags=L.F_QUICKGELU)
+            if erf_gelu:  # (hidden_act "gelu": a plain fc1 launch, then the exact GELU in place)
+                hmid = self.gelu(P, self.conv(P, x, pk.pack(p + nm["fc1"], ln=p + nm["ln2"]), ln_eps=eps))
+            else:
+                hmid = self.conv(P, x, pk.pack(p + nm["fc1"], ln=p + nm["ln2"]), ln_eps=eps, flags=L.F_QUICKGELU)
             x = self.conv(P, hmid, pk.pack(p + nm["fc2"]), residual=x)
         g, b_ = pk.vec(nm["final"] + ".weight"), pk.vec(nm["final"] + ".bias")
         fn_l = self.lib.upk_layernorm_f16
@@ -192,7 +206,8 @@ class _TextTower(ParamTree):
         self._plans = {}
         self._fp = None
 
-    def _run(self, input_ids):
+    def _plan(self, B):
+        """The launch program for batch size B of the calling thread's lane (built on first use)."""
         p = next(self.parameters())
         if p.device.type != "cuda":
             raise RuntimeError("upgpt_amd.%s computes only through the HIP kernels on an MI355X: move it to 'cuda' first. "
@@ -202,7 +217,6 @@ class _TextTower(ParamTree):
             fp = weights_fingerprint(self)
             if fp != self._fp:
                 self._plans, self._fp, self._packs = {}, fp, SharedPacks()
-            B = int(input_ids.shape[0])
             key = (B, concurrency() > 1, current_lane())
             plan = self._plans.get(key)
             if plan is None:
@@ -215,6 +229,11 @@ class _TextTower(ParamTree):
                                                         names=self.NAMES, shared=self._packs)
                     if self._packs.take_fresh():
                         torch.cuda.current_stream(p.device).synchronize()
+        return plan
+
+    def _run(self, input_ids):
+        plan = self._plan(int(input_ids.shape[0]))
+        p = next(self.parameters())
         from ._lib import host_io
         with torch.cuda.device(p.device):
             plan.check(input_ids)

@@ -380,6 +380,14 @@ class Emitter:
         P.meta[-1] = d
         return ret
 
+    def gelu(self, P, x):
+        """Exact (erf) GELU in place over the Act `x` (upk_gelu_f16): the activation of a CLIP MLP whose hidden_act is
+        "gelu", behind a plain fc1 launch (the quick_gelu towers keep theirs in the GEMM epilogue)."""
+        fn, h, chk = self.lib.upk_gelu_f16, self.hctx, self._chk
+        a = (x.t.data_ptr(), x.ld, x.M, x.C)
+        P.add(lambda s: chk(fn(h, *a, s)), x, cls="other", label="gelu M%d C%d" % (x.M, x.C))
+        return x
+
     class GnProvider:
         """A launch other than upk_conv2d_nhwc_f16 that leaves the per-(row block, channel) GroupNorm partials of its
         output (mode 2 of include/upk.h gn_stats_ws): (stats buffer, nblk, ld) are fixed when it is emitted."""

@@ -125,12 +125,19 @@ def interp_mask(src_mask, dst_mask, alpha):
     return get_mask(src_mask, coord)
 
 
-def load_clip_weights(path, text_encoder=None, image_encoder=None):
+def load_clip_weights(path, text_encoder=None, image_encoder=None, cond_stage=None):
     """Loads a state dict of the `clip` package's CLIP model (as `clip.load(name, jit=False)[0].state_dict()` saves it:
     `visual.*`, `transformer.*`, `token_embedding.weight`, `positional_embedding`, `ln_final.*`, `text_projection`,
-    `logit_scale`) into the text tower and/or the image tower."""
+    `logit_scale`) into the text tower and/or the image tower.
+    cond_stage: a CLIPTextImageCrossAtten; `path` then holds the state dict of transformers' `CLIPModel` (as
+    `CLIPModel.from_pretrained(version).state_dict()` saves it), loaded into `cond_stage.model`; `position_ids`
+    buffers of older transformers versions are ignored."""
     sd = torch.load(path, map_location="cpu", weights_only=False)
     sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd.state_dict()
+    if cond_stage is not None:
+        want = cond_stage.model.state_dict()
+        cond_stage.model.load_state_dict({k: sd[k].float().reshape(want[k].shape) for k in want})
+        return
     if text_encoder is not None:
         want = text_encoder.model.state_dict()
         text_encoder.model.load_state_dict({k: sd[k].float() for k in want})
