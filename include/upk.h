@@ -235,15 +235,20 @@ int upk_conv_ln_rows(upk_ctx* ctx, const upk_conv_desc* d, int* slots);
 
 /* Fused feed-forward tail of a SpatialTransformer block — BasicTransformerBlock.norm3 -> FeedForward (GEGLU, erf GELU)
  * -> + residual (attention.py:42-64, 215) followed by SpatialTransformer.proj_out -> + x_in (attention.py:259-261) —
- * as ONE launch; the 4c-wide hidden activation stays in LDS:
+ * as ONE launch; the 4c-wide hidden activation stays on the CU (the resident form keeps all of it in LDS, the streaming
+ * form two 128-column slices of it):
  *     h   = (xn W1v^T + b1v) * gelu(xn W1g^T + b1g),  xn = LayerNorm(x)          [m, inner]
  *     y   = residual + [h | x] W2^T + b2                                          [m, n_out]
  * x: un-normalised rows [m, ldx] (c channels, c % 224 == 0); w1 / b1 / u1: the GEGLU Linear packed as for
  * upk_conv2d_nhwc_f16 with UPK_F_GEGLU and ln_colsum (W * gamma in [32 value | 32 gate] row blocks, b + W beta, column
  * sums of the fp16-rounded rows), inner = 4 c; w2: packed [n_pad rows][K = inner + c] weight whose K order is [h | x]
- * (Packer.append_1x1(P F2, P) for ff.net.2 / proj_out), b2 [n_pad]; n_pad <= 256.  rows_per_wg: 32 or 64 (0 = 64).
+ * (Packer.append_1x1(P F2, P) for ff.net.2 / proj_out), b2 [n_pad]; n_pad <= 256.  rows_per_wg: 32 or 64 (0 = 64): the resident
+ * form, for a launch that has the chip to itself; 128, or 64 | UPK_MLP_STREAM: the streaming form (c = 224 only), whose
+ * m / 128 workgroups stream the weights a quarter as often, for launches that share the chip with other batches.  Same K order
+ * per row in both forms: at equal rows the results are bit-identical.
  * gn_stats_ws != NULL: per-(row block, channel) GroupNorm partials [m / hw][hw / rows_per_wg][2][n_pad] of y, as
  * upk_conv_desc.gn_stats_ws mode 2 (hw = rows per sample, a multiple of rows_per_wg). */
+#define UPK_MLP_STREAM 0x1000 /* or-ed into upk_mlp_desc.rows_per_wg: the streaming form at that tile height */
 typedef struct upk_mlp_desc {
   const void* x;
   int32_t ldx, m, c, inner;
@@ -263,7 +268,10 @@ typedef struct upk_mlp_desc {
   int32_t hw, rows_per_wg;
 } upk_mlp_desc;
 int upk_geglu_mlp_f16(upk_ctx* ctx, const upk_mlp_desc* d, upk_stream stream);
-/* 1 if upk_geglu_mlp_f16 takes the shape (channel family, LDS budget, row-block geometry), else 0. */
+/* 1 if upk_geglu_mlp_f16 takes the shape, else 0: the 7 * 32 channel family, n_pad <= 256, rows_per_wg one of the values above,
+ * the LDS of the form within 160 KB — resident (5 c / 32) * rows * 64 B, i.e. c = 224 up to 64 rows; streaming (c / 32 + 8) * rows
+ * * 64 B, i.e. c = 224 up to 128 rows and c = 448 refused at 128 — and, with gn_stats_ws, hw a multiple of rows with at most 32
+ * row blocks per sample. */
 int upk_geglu_mlp_supported(upk_ctx* ctx, const upk_mlp_desc* d);
 
 /* The cross-attention half of a BasicTransformerBlock (attention.py:257-260 with the context K / V precomputed) as one

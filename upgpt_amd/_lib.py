@@ -84,6 +84,9 @@ class ConvDesc(C.Structure):
     ]
 
 
+MLP_STREAM = 0x1000  # UPK_MLP_STREAM (include/upk.h): or-ed into MlpDesc.rows_per_wg, the streaming form at that height
+
+
 class MlpDesc(C.Structure):
     """Mirror of struct upk_mlp_desc (include/upk.h)."""
     _fields_ = [

@@ -12,12 +12,22 @@
 //
 // The price is the weight traffic per CU: every workgroup streams BOTH weights in full ((8 + 5) C^2 fp16), where the
 // two-launch form tiles N.  It pays where M / BM covers the chip (the 32x32 level: M = 8192), not at the deeper levels.
+//
+// Two forms.  mlp_kernel<2 | 4, 7> (32 / 64 rows) is the RESIDENT form above: the whole h tile in LDS ((4C + C) / 32
+// chunks x BM x 64 B: 140 KB at 64 rows, so no taller tile), one launch that has the chip to itself — 256 workgroups at
+// M = 8192.  mlp_stream_kernel<4, 7 | 8, 4> (64 / 128 rows, C = 224) is the STREAMING form further down: h exists only as
+// two 128-column slices (t2 tile + 2 x 4 chunks: 15 x BM x 64 B = 120 KB at 128 rows), the second GEMM's accumulators stay
+// in registers across the GEGLU passes.  At 128 rows a launch is 64 workgroups that stream the weights a quarter as often:
+// the form for launches that share the chip with other batches.  Same K order per row: equal BM, equal bits.
 #include "igemm_common.h"
 
 namespace upkd {
 namespace {
 
 constexpr int ML_NW = 8;
+#ifndef UPK_MLP_SLICES
+#define UPK_MLP_SLICES 2  // (1 in dev builds: one h slice and a second barrier per pass — the A/B of DESIGN.md 26)
+#endif
 
 struct MlpArgs {
   const f16* x;      // t2 [M, ldx] (un-normalised residual stream)
@@ -307,10 +317,301 @@ __global__ __launch_bounds__(512) void mlp_kernel(const MlpArgs s) {
 #undef STAMP
 }
 
+template <int I>
+struct ml_ic {
+  static constexpr int value = I;
+};
+template <int B, int E, class F>
+__device__ __forceinline__ void ml_static_for(F&& f) {  // f(ml_ic<B>) .. f(ml_ic<E - 1>): a loop whose index is a constant
+  if constexpr (B < E) {
+    f(ml_ic<B>{});
+    ml_static_for<B + 1, E>(f);
+  }
+}
+
+// The streaming form: the same computation with the same operands, but h never exists as a whole tile.  The second
+// GEMM's accumulators (wave w: its 32 output columns, MI x 2 fragments) live in registers for the whole kernel; each
+// GEGLU pass writes its 128 hidden columns — 4 K chunks of the second GEMM — into one of two LDS slices, and behind ONE
+// workgroup barrier every wave feeds those 4 chunks to its accumulators while the other slice is free for the next pass
+// (a wave that writes slice p & 1 again in pass p + 2 has passed the barrier of pass p + 1, which no wave reaches before
+// it has consumed pass p).  After the last pass the t2 chunks are consumed from the resident tile: the K order of a row
+// is the resident kernel's (hidden chunks ascending, then t2), so at equal BM the results are bit-identical.
+// One weight ring of RD slots carries both streams.  A pass is NK1 + 4 steps (7 chunks of w1, 4 of w2), unrolled; step t
+// consumes slot t % RD and refills it with step t + RD of the pass or, in its last RD steps, with step t % RD of the
+// next pass (behind the last pass: of the t2 chunks of w2) — every fragment is requested >= min(RD, 3) steps before its
+// use, and a pass starts with its steps 0 .. RD - 1 in slots 0 .. RD - 1 whatever (NK1 + 4) % RD is.
+template <int MI, int RD>
+__global__ __launch_bounds__(512) void mlp_stream_kernel(const MlpArgs s) {
+  constexpr int NW = ML_NW, NI = 2;
+  constexpr int BM = MI * 16;
+  constexpr int PW = NW * NI * 16;  // packed GEGLU columns per pass (= 128 hidden columns)
+  constexpr int NK1 = 7;            // K chunks of a GEGLU pass (c = 224: n_pad <= 256 leaves no other member of the family)
+  constexpr int NS = PW / 64;       // hidden chunks per pass = K chunks of the second GEMM per slice
+  constexpr int S = NK1 + NS;
+  constexpr int NSL = UPK_MLP_SLICES;
+  static_assert(RD >= 1 && RD <= NK1, "the first RD steps of a pass are w1 chunks (t2 chunks behind the last pass)");
+  extern __shared__ __attribute__((aligned(16))) f16 smem[];
+  ML_PIN(s.x); ML_PIN(s.w1); ML_PIN(s.w2); ML_PIN(s.zero); ML_PIN(s.b1); ML_PIN(s.u1); ML_PIN(s.b2); ML_PIN(s.res);
+  ML_PIN(s.y); ML_PIN(s.gn_cp); ML_PIN(s.ldx); ML_PIN(s.ldr); ML_PIN(s.ldy); ML_PIN(s.M); ML_PIN(s.nch1); ML_PIN(s.n1);
+  ML_PIN(s.n2); ML_PIN(s.n2pad); ML_PIN(s.nh);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lg = lane >> 4, lc = lane & 15;
+  const int m0 = upk_xcd_tile(blockIdx.x, gridDim.x) * BM;
+  const int nh = s.nh;
+  // LDS: the t2 tile (NK1 chunks), two slices of NS chunks of h, the row statistics, the GEGLU vectors
+  f16* const xT = smem;
+  f16* const hS = smem + NK1 * BM * 32;
+  float* const st = (float*)(smem + (NK1 + NSL * NS) * BM * 32);  // [BM][2]
+  float* const bl = st + BM * 2;                                // [2][n1]: GEGLU bias, LayerNorm column sums (packed order)
+
+  // ---- 1. t2 tile and the GEGLU epilogue's vectors (as mlp_kernel)
+  {
+    typedef __attribute__((address_space(3))) void* lds_ptr;
+    typedef const __attribute__((address_space(1))) void* glb_ptr;
+    const int r16 = lane >> 2;
+    const int chd = (lane & 3) ^ ((-(lane >> 4)) & 3);
+    const f16* zsrc = s.zero + (lane & 3) * 8;
+    for (int idx = wave; idx < NK1 * MI; idx += NW) {
+      const int kc = idx / MI, rg = idx - kc * MI;
+      const int m = m0 + rg * 16 + r16;
+      const f16* src = m < s.M ? s.x + (long)m * s.ldx + kc * 32 + chd * 8 : zsrc;
+      __builtin_amdgcn_global_load_lds((glb_ptr)src, (lds_ptr)(xT + (kc * BM + rg * 16) * 32), 16, 0, 0);
+    }
+    const int nkb = s.n1 >> 8;  // 1 KiB pieces per array (n1 % 256 == 0)
+    for (int idx = wave; idx < 2 * nkb; idx += NW) {
+      const float* src = (idx < nkb ? s.b1 + idx * 256 : s.u1 + (idx - nkb) * 256) + lane * 4;
+      __builtin_amdgcn_global_load_lds((glb_ptr)src, (lds_ptr)(bl + idx * 256), 16, 0, 0);
+    }
+  }
+
+  // ---- 2. weight streams: the column ownership of mlp_kernel.  n1 % PW == 0, so every wave has columns in every pass.
+  // A wave without columns in the second GEMM (act2 false) runs its steps all the same, on the first 2 KiB of w2 over and
+  // over (chunk stride 0: hits in its L1) and into accumulators nobody reads: a branch around them would cost every wave
+  // the compiler's vmcnt count (it drains the ring at each join), and that wave's SIMD is no busier than the other three.
+  const int col1 = (wave >> 1) * 64 + (wave & 1) * 16;
+  const int npass = s.n1 / PW;
+  const int col2 = wave * 32;
+  const bool act2 = col2 < s.n2pad;
+  const unsigned ks1 = (unsigned)s.n1 * 64u, ks2 = act2 ? (unsigned)s.n2pad * 64u : 0u;
+  const unsigned loff = (unsigned)(lc * 32 + lg * 8) * 2u;
+  const char* wb1 = (const char*)s.w1 + (size_t)col1 * 64;
+  const char* wb2 = (const char*)s.w2 + (size_t)(act2 ? col2 : 0) * 64;
+  const char* const wt2 = wb2 + (size_t)((unsigned)nh * ks2);  // w2's t2 chunks
+  f16x8 ring[RD][NI];
+#pragma unroll
+  for (int u = 0; u < RD; ++u) {
+    ring[u][0] = *(const f16x8*)(wb1 + (unsigned)u * ks1 + loff);
+    ring[u][1] = *(const f16x8*)(wb1 + (unsigned)u * ks1 + 2048 + loff);
+  }
+  __syncthreads();  // (t2 tile landed)
+
+  // ---- 3. LayerNorm statistics of the tile's rows (from the resident tile)
+  {
+    constexpr int LPR = 512 / BM;
+    const int row = tid / LPR, part = tid - row * LPR;
+    float s1 = 0.f, s2 = 0.f;
+    const f16x2 one2 = {(f16)1.f, (f16)1.f};
+    for (int q = part; q < NK1 * 4; q += LPR) {
+      const f16x8 v = *(const f16x8*)(xT + ((q >> 2) * BM + row) * 32 + (q & 3) * 8);
+#pragma unroll
+      for (int h = 0; h < 4; ++h) {
+        const f16x2 xx = {v[2 * h], v[2 * h + 1]};
+        s1 = __builtin_amdgcn_fdot2(xx, one2, s1, false);
+        s2 = __builtin_amdgcn_fdot2(xx, xx, s2, false);
+      }
+    }
+#pragma unroll
+    for (int o = 1; o < LPR; o <<= 1) {
+      s1 += __shfl_xor(s1, o);
+      s2 += __shfl_xor(s2, o);
+    }
+    if (part == 0) {
+      const float mu = s1 * s.ln_inv_dim;
+      st[2 * row] = mu;
+      st[2 * row + 1] = rsqrtf(fmaxf(s2 * s.ln_inv_dim - mu * mu, 0.f) + s.ln_eps);
+    }
+  }
+  __syncthreads();
+
+  const unsigned la = (unsigned)(lc * 32 + lds_swz(lc, lg) * 8) * 2u;
+  const char* const xs = (const char*)xT + la;
+  f32x4 acc[MI][NI];  // the second GEMM's
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NI; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  // ---- 4. passes: GEGLU over the t2 tile -> slice p & 1 -> barrier -> the slice's 4 chunks into the second GEMM
+#pragma unroll 1
+  for (int p = 0; p < npass; ++p) {
+    const bool last = p + 1 >= npass;
+    const char* const g1 = wb1 + (size_t)((unsigned)(p * PW) * 64u);         // this pass's w1 columns
+    const char* const g2 = wb2 + (size_t)((unsigned)(p * NS) * ks2);         // this pass's w2 chunks
+    const char* const nx = last ? wt2 : g1 + PW * 64;                        // the first RD steps of what follows
+    const unsigned ksn = last ? ks2 : ks1, fn = last ? 1024u : 2048u;
+    f16* const hT = hS + (p % NSL) * (NS * BM * 32);
+    auto refill = [&](auto tc) {
+      constexpr int t = decltype(tc)::value, q = t + RD, sl = t % RD;
+      if constexpr (q < NK1) {
+        ring[sl][0] = *(const f16x8*)(g1 + (unsigned)q * ks1 + loff);
+        ring[sl][1] = *(const f16x8*)(g1 + (unsigned)q * ks1 + 2048 + loff);
+      } else if constexpr (q < S) {
+        ring[sl][0] = *(const f16x8*)(g2 + (unsigned)(q - NK1) * ks2 + loff);
+        ring[sl][1] = *(const f16x8*)(g2 + (unsigned)(q - NK1) * ks2 + 1024 + loff);
+      } else {
+        ring[sl][0] = *(const f16x8*)(nx + (unsigned)sl * ksn + loff);
+        ring[sl][1] = *(const f16x8*)(nx + (unsigned)sl * ksn + fn + loff);
+      }
+    };
+    f32x4 ag[MI][NI];
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < NI; ++j) ag[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    ml_static_for<0, NK1>([&](auto tc) {
+      constexpr int t = decltype(tc)::value;
+      f16x8 fc[MI];
+#pragma unroll
+      for (int i = 0; i < MI; ++i) fc[i] = *(const f16x8*)(xs + (t * BM + i * 16) * 64);
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < NI; ++j)
+          ag[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ring[t % RD][j], fc[i], ag[i][j], 0, 0, 0);
+      refill(tc);
+      __builtin_amdgcn_sched_barrier(0);
+    });
+    {  // epilogue: folded LayerNorm, bias, v * gelu(g) -> fp16 -> slice (chunk = wave / 2; layout as mlp_kernel's h tile)
+      const int n = col1 + p * PW + lg * 4;  // packed value column
+      const f32x4 bv0 = *(const f32x4*)(bl + n), bv1 = *(const f32x4*)(bl + n + 32);
+      const f32x4 lu0 = *(const f32x4*)(bl + s.n1 + n), lu1 = *(const f32x4*)(bl + s.n1 + n + 32);
+      const int oc = n & 31;  // hidden column inside its chunk
+      const int hk = wave >> 1, hq = oc >> 3, hh = oc & 7;
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        const f32x2 mr = *(const f32x2*)(st + 2 * (i * 16 + lc));
+        const f32x4 v = (ag[i][0] - mr[0] * lu0) * mr[1] + bv0;
+        const f32x4 g = (ag[i][1] - mr[0] * lu1) * mr[1] + bv1;
+        f16x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = (f16)upk_geglu_mul(v[k], g[k]);
+        const int row = i * 16 + lc;
+        *(f16x4*)(hT + (hk * BM + row) * 32 + lds_swz(lc, hq) * 8 + hh) = o;
+      }
+    }
+    __syncthreads();  // (slice p & 1 complete)
+    const char* const hs = (const char*)hT + la;
+    ml_static_for<NK1, S>([&](auto tc) {
+      constexpr int t = decltype(tc)::value;
+      f16x8 fc[MI];
+#pragma unroll
+      for (int i = 0; i < MI; ++i) fc[i] = *(const f16x8*)(hs + ((t - NK1) * BM + i * 16) * 64);
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < NI; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ring[t % RD][j], fc[i], acc[i][j], 0, 0, 0);
+      refill(tc);
+      __builtin_amdgcn_sched_barrier(0);
+    });
+    if constexpr (NSL == 1) __syncthreads();  // (the slice is free again)
+  }
+
+  // ---- 5. the t2 chunks of the second GEMM from the resident tile; epilogue: bias, residual, GroupNorm partials
+  if (!act2) return;
+  f32x4 b2v[NI];
+  f16x4 rr[MI][NI];
+#pragma unroll
+  for (int j = 0; j < NI; ++j) {
+    const int n = col2 + j * 16 + lg * 4;
+    b2v[j] = *(const f32x4*)(s.b2 + n);
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+      const unsigned m = (unsigned)min(m0 + i * 16 + lc, s.M - 1);
+      rr[i][j] = *(const f16x4*)(s.res + m * (unsigned)s.ldr + (unsigned)(n < s.n2 ? n : 0));
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  ml_static_for<0, NK1>([&](auto tc) {
+    constexpr int t = decltype(tc)::value;
+    f16x8 fc[MI];
+#pragma unroll
+    for (int i = 0; i < MI; ++i) fc[i] = *(const f16x8*)(xs + (t * BM + i * 16) * 64);
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < NI; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ring[t % RD][j], fc[i], acc[i][j], 0, 0, 0);
+    if constexpr (t + RD < NK1) {
+      ring[t % RD][0] = *(const f16x8*)(wt2 + (unsigned)(t + RD) * ks2 + loff);
+      ring[t % RD][1] = *(const f16x8*)(wt2 + (unsigned)(t + RD) * ks2 + 1024 + loff);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  });
+  f32x4 cs[NI], cq[NI];
+#pragma unroll
+  for (int j = 0; j < NI; ++j) cs[j] = cq[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < MI; ++i) {
+    const int m = m0 + i * 16 + lc;
+    const bool ok = m < s.M;
+    f16* yrow = s.y + (unsigned)(ok ? m : 0) * (unsigned)s.ldy;
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+      const int n = col2 + j * 16 + lg * 4;
+      const f32x4 v = acc[i][j] + b2v[j];
+      f16x4 o;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = (f16)(v[k] + (float)rr[i][j][k]);
+      if (ok && n < s.n2) *(f16x4*)(yrow + n) = o;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float f = ok ? (float)o[k] : 0.f;
+        cs[j][k] += f;
+        cq[j][k] += f * f;
+      }
+    }
+  }
+  if (s.gn_cp) {
+    const int b = m0 / s.gn_hw;
+    const int blk = (m0 - b * s.gn_hw) / BM;
+    float* dst = s.gn_cp + (long)((b * s.gn_nblk + blk) * 2) * s.n2pad;
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+      const int n = col2 + j * 16 + lg * 4;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        cs[j][k] = Epi::row_sum16(cs[j][k]);
+        cq[j][k] = Epi::row_sum16(cq[j][k]);
+      }
+      if (lc == 0) {
+        *(f32x4*)(dst + n) = cs[j];
+        *(f32x4*)(dst + s.n2pad + n) = cq[j];
+      }
+    }
+  }
+}
+
 }  // namespace
 }  // namespace upkd
 
 using namespace upkd;
+
+// rows_per_wg -> (rows, form): 32 / 64 the resident kernels, 128 and 64 | UPK_MLP_STREAM the streaming ones (0 = 64 resident)
+static int mlp_form(const upk_mlp_desc* d, int* stream) {
+  const int raw = d->rows_per_wg > 0 ? d->rows_per_wg : 64;
+  const int bm = (raw & ~UPK_MLP_STREAM) ? (raw & ~UPK_MLP_STREAM) : 64;
+  *stream = (raw & UPK_MLP_STREAM) != 0 || bm == 128;
+  return bm;
+}
+
+// LDS of a launch: the resident form keeps [h | t2] (nh + nch1 chunks), the streaming form t2 and two 4-chunk slices of h
+static size_t mlp_lds_bytes(int nch1, int nh, int n1, int bm, int stream) {
+  return (size_t)(stream ? nch1 + 4 * UPK_MLP_SLICES : nch1 + nh) * bm * 64 + (size_t)bm * 8 + (size_t)n1 * 8;
+}
 
 extern "C" int upk_geglu_mlp_supported(upk_ctx* ctx, const upk_mlp_desc* d) {
   if (!ctx || !d) return 0;
@@ -319,10 +620,12 @@ extern "C" int upk_geglu_mlp_supported(upk_ctx* ctx, const upk_mlp_desc* d) {
   if (nch1 % 7 || (nch1 + nh) % 7) return 0;   // (ring depth 7: the 7 * 32 channel family)
   if (d->n_pad > ML_NW * 32 || (d->n_pad & 31)) return 0;
   if ((d->ldx & 7) || (d->ld_res & 3) || (d->ldy & 3) || (d->n_out & 3)) return 0;
-  const int bm = d->rows_per_wg > 0 ? d->rows_per_wg : 64;
-  if (bm != 32 && bm != 64) return 0;
+  int stream;
+  const int bm = mlp_form(d, &stream);
+  if (stream ? (bm != 64 && bm != 128) : (bm != 32 && bm != 64)) return 0;
   if ((2 * d->inner) & 255) return 0;
-  if ((size_t)(nch1 + nh) * bm * 64 + (size_t)bm * 8 + (size_t)d->inner * 16 > 160 * 1024) return 0;
+  if (mlp_lds_bytes(nch1, nh, 2 * d->inner, bm, stream) > 160 * 1024) return 0;  // (c = 448 at 128 rows: 114 + 64 KB)
+  if (stream && nch1 != 7) return 0;  // (a pass of the streaming form is unrolled over its 7 K chunks)
   if (d->gn_stats_ws && (d->hw <= 0 || d->hw % bm || d->hw / bm > UPK_GN_MAX_CHUNKS)) return 0;
   return 1;
 }
@@ -342,7 +645,8 @@ extern "C" int upk_geglu_mlp_f16(upk_ctx* ctx, const upk_mlp_desc* d, upk_stream
   s.gn_cp = d->gn_stats_ws;
   s.ldx = d->ldx, s.ldr = d->ld_res, s.ldy = d->ldy, s.M = d->m;
   s.nch1 = d->c / 32, s.n1 = 2 * d->inner, s.n2 = d->n_out, s.n2pad = d->n_pad, s.nh = d->inner / 32;
-  const int bm = d->rows_per_wg > 0 ? d->rows_per_wg : 64;
+  int strm;
+  const int bm = mlp_form(d, &strm);
   s.gn_hw = d->hw > 0 ? d->hw : 1;
   s.gn_nblk = d->hw > 0 ? d->hw / bm : 1;
   s.ln_inv_dim = 1.0f / (float)(d->ln_dim > 0 ? d->ln_dim : d->c);
@@ -350,10 +654,11 @@ extern "C" int upk_geglu_mlp_f16(upk_ctx* ctx, const upk_mlp_desc* d, upk_stream
 #ifdef UPK_TIMELINE
   s.dbg = getenv("UPK_MLP_TL") ? (unsigned long long*)((char*)ctx->ws + ctx->ws_bytes - 4096) : nullptr;
 #endif
-  const size_t lds = (size_t)(s.nch1 + s.nh) * bm * 64 + (size_t)bm * 8 + (size_t)s.n1 * 8;
-  void (*fn)(const MlpArgs) = bm == 32 ? mlp_kernel<2, 7> : mlp_kernel<4, 7>;
-  static unsigned long long attr32 = 0, attr64 = 0;
-  if (int rc = upk_lds_attr_once(ctx, (const void*)fn, bm == 32 ? &attr32 : &attr64)) return rc;
+  const size_t lds = mlp_lds_bytes(s.nch1, s.nh, s.n1, bm, strm);
+  void (*fn)(const MlpArgs) = strm ? (bm == 64 ? mlp_stream_kernel<4, 7> : mlp_stream_kernel<8, 4>)
+                                     : (bm == 32 ? mlp_kernel<2, 7> : mlp_kernel<4, 7>);
+  static unsigned long long attr[4] = {0, 0, 0, 0};
+  if (int rc = upk_lds_attr_once(ctx, (const void*)fn, &attr[strm * 2 + (bm > (strm ? 64 : 32))])) return rc;
   upk_prof_scope prof(ctx, UPK_CLS_IGEMM, stream);
   hipLaunchKernelGGL(fn, dim3((s.M + bm - 1) / bm), dim3(512), lds, stream, s);
   return upk_check_launch(ctx, "geglu_mlp");

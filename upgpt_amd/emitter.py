@@ -494,7 +494,7 @@ class Emitter:
 
     def mlp_rows(self, M):
         """Rows per workgroup of the fused feed-forward kernel: 64 while that still gives every CU a workgroup."""
-        if K.MLP_ROWS in (32, 64):
+        if K.MLP_ROWS in (32, 64, 128):
             return K.MLP_ROWS
         return 64 if M // 64 >= self.ctx.num_cus else 32
 
@@ -505,13 +505,18 @@ class Emitter:
         if K.MLP_FUSE == "0" or t2.C != t2.ld:
             return None
         M, C_ = t2.M, t2.C
-        if (K.MLP_FUSE == "auto" and L.concurrency() > 1 and os.environ.get("UPGPT_LANES_TUNING", "1") == "1"
+        # a forced tile height, or with several batches in flight the one stored with the shared-chip table ("__mlp_rows__":
+        # the streaming form): either one keeps the launch fused and goes before "__unfuse_mlp_M__", which
+        # stays the answer for the resident form and wherever the stored height is outside the kernel's domain
+        rows = self.row_chain_rows("mlp", M, 0)
+        if (not rows and K.MLP_FUSE == "auto" and L.concurrency() > 1 and os.environ.get("UPGPT_LANES_TUNING", "1") == "1"
                 and M in TUNE_CACHE_LANES.meta.get("__unfuse_mlp_M__", ())):
             # several batches in flight: the kernel holds every CU with one register-heavy workgroup that streams both
             # weights (21 us of chip time per launch); GEGLU + (ff.net.2 o proj_out) as two launches on tiles tuned for a
             # shared chip cost less (forward in flight 1.524 -> 1.490 ms) — for the row counts the table lists
             return None
-        rows = self.mlp_rows(M)
+        rows = rows or self.mlp_rows(M)
+        stream = rows == 128 or (rows == 64 and K.MLP_STREAM)
         d = L.MlpDesc()
         d.x, d.ldx, d.m, d.c, d.inner = t2.t.data_ptr(), t2.ld, M, C_, pw1.n_out
         d.w1, d.b1, d.u1 = pw1.w.data_ptr(), pw1.bias.data_ptr(), pw1.ln_colsum.data_ptr()
@@ -519,11 +524,13 @@ class Emitter:
         d.w2, d.b2, d.n_out, d.n_pad = pw2.w.data_ptr(), pw2.bias.data_ptr(), pw2.n_out, pw2.n_pad
         d.residual, d.ld_res = x_in.t.data_ptr(), x_in.ld
         hw = t2.H * t2.W
-        d.hw, d.rows_per_wg = hw, rows
+        d.hw, d.rows_per_wg = hw, rows | (L.MLP_STREAM if stream else 0)
         if not self.lib.upk_geglu_mlp_supported(self.hctx, C.byref(d)):
             return None
-        if K.MLP_FUSE == "auto" and (M + rows - 1) // rows < (self.ctx.num_cus * 3) // 4:
-            return None  # (every workgroup streams both weights in full: it pays only when M / rows covers the chip)
+        if K.MLP_FUSE == "auto" and (M + min(rows, 32) - 1) // min(rows, 32) < (self.ctx.num_cus * 3) // 4:
+            # (every workgroup streams both weights in full: it pays only when M covers the chip — a test made at 32 rows,
+            # as head_block_ok's: the tall forms are chosen in order NOT to cover it)
+            return None
         out = Act(self.alloc(M, pw2.n_out), t2.B, t2.H, t2.W, pw2.n_out)
         d.y, d.ldy = out.t.data_ptr(), out.ld
         sws = None
@@ -533,21 +540,24 @@ class Emitter:
             out.gn_src = Emitter.GnProvider(sws, hw // rows, pw2.n_pad)
         fn, h, chk = self.lib.upk_geglu_mlp_f16, self.hctx, self._chk
         P.add(lambda s: chk(fn(h, C.byref(d), s)), d, t2, x_in, pw1, pw2, out, sws, cls="igemm_k1",
-              label="mlp M%d C%d rows%d" % (M, C_, rows))
+              label="mlp M%d C%d rows%d%s" % (M, C_, rows, "s" if stream else ""))
         P.igemm_flops += 2 * M * (2 * pw1.n_out * C_ + pw2.n_real * (pw1.n_out + C_))
         P.flops[-1] = 2 * M * (2 * pw1.n_out * C_ + pw2.n_real * (pw1.n_out + C_))
         return out
 
     def row_chain_rows(self, kind, M, default=32):
-        """Rows per workgroup of a row-chain kernel (kind: "hblock" | "xblock") on an M-row tensor: a forced value
-        (UPGPT_HB_ROWS for the head, UPGPT_XB_ROWS for both), else, with several batches in flight, the decision stored
-        with the shared-chip table ("__row_chain_rows__": {kind: {M: rows}} — 64 workgroups of 128 rows hold a quarter of
-        the chip and stream the weights a quarter as often), else `default`."""
-        forced = (K.HB_ROWS if kind == "hblock" else 0) or K.XB_ROWS
+        """Rows per workgroup of a row-chain kernel (kind: "hblock" | "xblock" | "mlp") on an M-row tensor: a forced value
+        (UPGPT_HB_ROWS for the head, UPGPT_XB_ROWS for both, UPGPT_MLP_ROWS for the feed-forward tail), else, with several
+        batches in flight, the decision stored with the shared-chip table ("__row_chain_rows__": {kind: {M: rows}}, for the
+        feed-forward tail "__mlp_rows__": {M: rows} — 64 workgroups of 128 rows hold a quarter of the chip and stream the
+        weights a quarter as often), else `default`."""
+        forced = K.MLP_ROWS if kind == "mlp" else (K.HB_ROWS if kind == "hblock" else 0) or K.XB_ROWS
         if forced:
             return forced
         if L.concurrency() > 1 and os.environ.get("UPGPT_LANES_TUNING", "1") == "1":
-            r = TUNE_CACHE_LANES.meta.get("__row_chain_rows__", {}).get(kind, {}).get(str(M))
+            tab = (TUNE_CACHE_LANES.meta.get("__mlp_rows__", {}) if kind == "mlp"
+                   else TUNE_CACHE_LANES.meta.get("__row_chain_rows__", {}).get(kind, {}))
+            r = tab.get(str(M))
             if r:
                 return int(r)
         return default

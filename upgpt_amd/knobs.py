@@ -19,7 +19,11 @@ GN_REDUCE_APPLY = os.environ.get("UPGPT_GN_REDUCE_APPLY", "1") == "1"
 # fused feed-forward tail (csrc/mlp.hip: GEGLU -> ff.net.2 o proj_out with the hidden activation in LDS): "auto" = where
 # M / rows-per-workgroup covers the chip (the 32x32 level at B = 8), "0" off, "1" wherever the kernel takes the shape
 MLP_FUSE = os.environ.get("UPGPT_MLP_FUSE", "auto")
-MLP_ROWS = int(os.environ.get("UPGPT_MLP_ROWS", "0"))  # rows per workgroup (32 / 64; 0 = by M)
+# rows per workgroup (32 / 64 / 128; 0 = by M, and with several batches in flight by the
+# "__mlp_rows__" decision of the shared-chip table).  128 rows exist in the streaming form only (h in two LDS slices);
+# MLP_STREAM picks that form at 64 rows too (A/Bs of the structure against the resident 64-row kernel)
+MLP_ROWS = int(os.environ.get("UPGPT_MLP_ROWS", "0"))
+MLP_STREAM = os.environ.get("UPGPT_MLP_STREAM", "0") == "1"
 # fused cross-attention half of a transformer block (csrc/xblock.hip: attn1.to_out -> norm2 -> to_q -> attention over the
 # context -> attn2.to_out, one launch instead of three / four): "auto", "0" off, "1" wherever the kernel takes the shape
 XBLOCK = os.environ.get("UPGPT_XBLOCK", "auto")

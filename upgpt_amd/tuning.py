@@ -24,7 +24,8 @@ class TuneCache:
         self.names = self.d.pop("__configs__", None)
         # other "__...__" keys are decisions that go with the table (e.g. "__unfuse_mlp_M__": row counts for which the fused
         # feed-forward tail loses to two launches tuned for a shared chip; "__row_chain_rows__": {"hblock" | "xblock":
-        # {M: rows per workgroup}} of the row-chain kernels on a shared chip); kept apart from the shape entries
+        # {M: rows per workgroup}} of the row-chain kernels on a shared chip, "__mlp_rows__": {M: rows per workgroup} the same
+        # for the fused feed-forward tail — it goes before "__unfuse_mlp_M__"); kept apart from the shape entries
         self.meta = {k: self.d.pop(k) for k in list(self.d) if k.startswith("__")}
         self._bound = False
 
