@@ -71,15 +71,16 @@ def ratio(got, ref, bound):
     return float(r.max())
 
 
-def activations(shape, seed, s=1, mu=None, sigma=None):
+def activations(shape, seed, s=1, mu=None, sigma=None, device="cpu"):
     """randn with |x| < 2^-10 replaced by +-2^-10, times s: fp16, no subnormal at any scale.  mu / sigma (broadcastable,
-    |mu| / sigma <= 4 is the caller's business) shift and stretch before the scaling."""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(*shape, generator=g)
+    |mu| / sigma <= 4 is the caller's business) shift and stretch before the scaling.  device: where the numbers are drawn
+    (tensors of 10^8 elements take seconds on the CPU; a device generator draws other numbers from the same seed)."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    x = torch.randn(*shape, generator=g, device=device)
     if sigma is not None:
-        x = x * sigma
+        x = x * sigma.to(device)
     if mu is not None:
-        x = x + mu
+        x = x + mu.to(device)
     tiny = x.abs() < 2.0 ** -10
     x = torch.where(tiny, torch.where(x < 0, -(2.0 ** -10), 2.0 ** -10) * torch.ones_like(x), x)
     return (x.half() * float(s)).half()
@@ -233,11 +234,14 @@ def _norm_terms(x, mean, msq, n, eps):
     return rstd, dmean, drstd
 
 
-def groupnorm_ref(x, groups, gamma, beta, eps, silu):
-    """x [B, hw, C] (fp64 of fp16 values), gamma / beta [C] -> ([B, hw, C], bound)."""
+def groupnorm_ref(x, groups, gamma, beta, eps, silu, dx=None):
+    """x [B, hw, C] (fp64 of fp16 values), gamma / beta [C] -> ([B, hw, C], bound).  dx [B, hw, C]: x is itself only known
+    to this bound (the kernel normalises ITS output, which is off from x by up to dx): pushed through the first-order map of
+    the normalisation, d xn = rstd (dx + mean dx) + |xn| rstd mean(|xn| dx) with xn = (x - mean) rstd, as in linear_ref."""
     B, hw, C = x.shape
     cpg = C // groups
-    xg = x.view(B, hw, groups, cpg).permute(0, 2, 1, 3).reshape(B, groups, hw * cpg)
+    grp = lambda t: t.reshape(B, hw, groups, cpg).permute(0, 2, 1, 3).reshape(B, groups, hw * cpg)
+    xg = grp(x)
     mean = xg.mean(-1, keepdim=True)
     msq = (xg * xg).mean(-1, keepdim=True)
     rstd, dmean, drstd = _norm_terms(xg, mean, msq, hw * cpg, eps)
@@ -246,6 +250,9 @@ def groupnorm_ref(x, groups, gamma, beta, eps, silu):
     y = (xg - mean) * rstd * gg + bb
     dy = gg.abs() * (rstd * dmean + (xg - mean).abs() * drstd) \
         + 4 * E32H * ((xg * rstd * gg).abs() + (mean * rstd * gg).abs() + bb.abs())
+    if dx is not None:
+        dg, xn = grp(dx), ((xg - mean) * rstd).abs()
+        dy = dy + gg.abs() * rstd * (dg + dg.mean(-1, keepdim=True) + xn * (xn * dg).mean(-1, keepdim=True))
     if silu:
         y, dy = _act(y, dy, "silu")
     dy = dy + u16(y)
@@ -393,7 +400,7 @@ def gemm_case_ref(o, splitk=1, out="f16", with_res=True):
     return linear_ref(d(o["a"]), q16(d(o["w"])), bias=d(o["bias"]), res=res, act=o["act"], out=out, splitk=splitk)
 
 
-def norm_input(shape, seed, s, chan_dim=-1):
+def norm_input(shape, seed, s, chan_dim=-1, device="cpu"):
     """Activations with a per-channel mean and spread: sigma_c in [1/8, 1/2] (a factor 4 between channels), |mu_c| up to
     2.8 sigma_c (near the |mu| / sigma <= 4 the issue allows, with room for the sample statistic), so that the largest
     scale stays inside fp16 (7.3 sigma 2^13 < 65504); groups and rows that mix channels have a smaller ratio (the host
@@ -403,7 +410,7 @@ def norm_input(shape, seed, s, chan_dim=-1):
     g = torch.Generator().manual_seed(seed + 99)
     sigma = 0.125 + 0.375 * torch.rand(C, generator=g)
     mu = (2 * torch.rand(C, generator=g) - 1) * 2.8 * sigma
-    return activations(shape, seed, s, mu=mu, sigma=sigma)
+    return activations(shape, seed, s, mu=mu, sigma=sigma, device=device)
 
 
 GN_CASES = {"gn96": (96, 0), "gn64_32": (64, 32)}  # (c1, c2), 32 groups, hw 48, B 2
@@ -523,9 +530,10 @@ def cross_case_ref(o):
 MLP_CASES = {"mlp96": (96, 32, 0), "mlp128": (128, 64, 64)}  # M, rows per workgroup, hw (0: no GroupNorm partials)
 
 
-def mlp_case(name, s):
-    """norm3 -> GEGLU -> h (fp16) -> ff.net.2 and proj_out in one GEMM over [h | x] (+ res); x and res scaled by s."""
-    M, rows, hw = MLP_CASES[name]
+def mlp_case(name, s, B=None, hw=None, rows=None):
+    """norm3 -> GEGLU -> h (fp16) -> ff.net.2 and proj_out in one GEMM over [h | x] (+ res); x and res scaled by s.
+    B, hw, rows: a shape of the caller's (B samples of hw rows, `rows` per workgroup) instead of MLP_CASES[name]."""
+    M, rows, hw = MLP_CASES[name] if B is None else (B * hw, rows, hw)
     c = 224
     inner = 4 * c
     return dict(M=M, rows=rows, hw=hw, c=c, inner=inner, x=norm_input((M, c), 41 + M, s), res=activations((M, c), 42, s),

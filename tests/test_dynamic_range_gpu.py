@@ -365,9 +365,9 @@ def test_attention_with_query_projection_inside_against_fp64(ctx, s):
     assert report("attention qproj", s, R.ratio(got[..., :dh].transpose(1, 2), ref, bound)) <= 1
 
 
-@pytest.mark.parametrize("s", R.SCALES)
-def test_head_block_against_fp64(ctx, s):
-    o = R.head_case(s)
+def launch_head_block(ctx, o, rows=16):
+    """One upk_head_block_f16 launch on head_case's operands at `rows` rows per workgroup; (t0, q | k, v) on the CPU, the
+    padded head columns taken out."""
     B, hw, c = o["B"], o["hw"], o["c"]
     heads, dh, dp = R.HEADS, R.DH, R.DP
     M, hd, inner = B * hw, heads * dp, heads * dh
@@ -390,23 +390,30 @@ def test_head_block_against_fp64(ctx, s):
     d.x, d.ldx, d.m, d.c, d.heads, d.d = x.data_ptr(), c, M, c, heads, dp
     d.w_in, d.w_qkv, d.vec, d.ln_eps, d.ln_dim = w1p.data_ptr(), w2p.data_ptr(), vec.data_ptr(), o["eps"], c
     d.t0, d.ld_t0, d.qk, d.ld_qk, d.vt, d.vt_ld = t0o.data_ptr(), c, qk.data_ptr(), 2 * hd, vt.data_ptr(), vt_ld
-    d.hw, d.rows_per_wg = hw, 16
+    d.hw, d.rows_per_wg = hw, rows
     assert ctx.lib.upk_head_block_supported(ctx.h, C.byref(d))
     ctx._chk(ctx.lib.upk_head_block_f16(ctx.h, C.byref(d), ctx._s()))
     torch.cuda.synchronize()
-    (t0, dt0), (qkv, dqkv) = R.head_case_ref(o)
-    assert float(t0.abs().max()) < 6e4 and float(qkv.abs().max()) < 6e4
-    assert report("head block t0", s, R.ratio(t0o.cpu(), t0, dt0)) <= 1
     real = (cols >= 0).cpu()
     got_qk = qk.cpu().view(M, 2, hd)[:, :, real].reshape(M, 2 * inner)
-    assert report("head block q | k", s, R.ratio(got_qk, qkv[:, :2 * inner], dqkv[:, :2 * inner])) <= 1
     got_v = vt.cpu()[..., :hw].permute(0, 3, 1, 2).reshape(M, hd)[:, real]
-    assert report("head block v", s, R.ratio(got_v, qkv[:, 2 * inner:], dqkv[:, 2 * inner:])) <= 1
+    return t0o.cpu(), got_qk, got_v
 
 
 @pytest.mark.parametrize("s", R.SCALES)
-def test_cross_block_against_fp64(ctx, s):
-    o = R.cross_case(s)
+def test_head_block_against_fp64(ctx, s):
+    o = R.head_case(s)
+    inner = R.HEADS * R.DH
+    t0o, got_qk, got_v = launch_head_block(ctx, o)
+    (t0, dt0), (qkv, dqkv) = R.head_case_ref(o)
+    assert float(t0.abs().max()) < 6e4 and float(qkv.abs().max()) < 6e4
+    assert report("head block t0", s, R.ratio(t0o, t0, dt0)) <= 1
+    assert report("head block q | k", s, R.ratio(got_qk, qkv[:, :2 * inner], dqkv[:, :2 * inner])) <= 1
+    assert report("head block v", s, R.ratio(got_v, qkv[:, 2 * inner:], dqkv[:, 2 * inner:])) <= 1
+
+
+def launch_cross_block(ctx, o, rows=16):
+    """One upk_cross_block_f16 launch on cross_case's operands at `rows` rows per workgroup; y on the CPU."""
     B, hw, c, nkv = o["B"], o["hw"], o["c"], o["nkv"]
     heads, dh, dp = R.HEADS, R.DH, R.DP
     M, hd, inner = B * hw, heads * dp, heads * dh
@@ -440,19 +447,25 @@ def test_cross_block_against_fp64(ctx, s):
     d.ln_eps, d.ln_dim = o["eps"], c
     d.k_ctx, d.ldk, d.n_kv = kc.data_ptr(), hd, nkv
     d.vt_ctx, d.vt_ld, d.scale = vt.data_ptr(), vt_ld, o["scale"]
-    d.y, d.ldy, d.hw, d.rows_per_wg = y.data_ptr(), c, hw, 16
+    d.y, d.ldy, d.hw, d.rows_per_wg = y.data_ptr(), c, hw, rows
     assert ctx.lib.upk_cross_block_supported(ctx.h, C.byref(d))
     ctx._chk(ctx.lib.upk_cross_block_f16(ctx.h, C.byref(d), ctx._s()))
     torch.cuda.synchronize()
-    ref, bound = R.cross_case_ref(o)
-    assert float(ref.abs().max()) < 6e4
-    assert report("cross block", s, R.ratio(y.cpu(), ref, bound)) <= 1
+    return y.cpu()
 
 
 @pytest.mark.parametrize("s", R.SCALES)
-@pytest.mark.parametrize("name", list(R.MLP_CASES))
-def test_mlp_tail_against_fp64(ctx, name, s):
-    o = R.mlp_case(name, s)
+def test_cross_block_against_fp64(ctx, s):
+    o = R.cross_case(s)
+    y = launch_cross_block(ctx, o)
+    ref, bound = R.cross_case_ref(o)
+    assert float(ref.abs().max()) < 6e4
+    assert report("cross block", s, R.ratio(y, ref, bound)) <= 1
+
+
+def launch_mlp_tail(ctx, o, rows_per_wg=None):
+    """One upk_geglu_mlp_f16 launch on mlp_case's operands (rows_per_wg: the descriptor's value, default o["rows"]);
+    (y, partials [B, nblk, 2, n_pad] or None) on the CPU."""
     M, rows, hw, c, inner = o["M"], o["rows"], o["hw"], o["c"], o["inner"]
     x, res, gamma, beta, w1, b1, w2h, w2x, b2 = _dev(o, "x", "res", "gamma", "beta", "w1", "b1", "w2h", "w2x", "b2")
     rm = geglu_row_map(inner).to(DEV)
@@ -469,7 +482,7 @@ def test_mlp_tail_against_fp64(ctx, name, s):
     d.w1, d.b1, d.u1, d.ln_eps, d.ln_dim = w1p.data_ptr(), b1p.data_ptr(), u1p.data_ptr(), o["eps"], c
     d.w2, d.b2, d.n_out, d.n_pad = w2p.data_ptr(), b2p.data_ptr(), c, n_pad
     d.residual, d.ld_res, d.y, d.ldy = res.data_ptr(), c, y.data_ptr(), c
-    d.rows_per_wg, d.hw = rows, hw
+    d.rows_per_wg, d.hw = rows if rows_per_wg is None else rows_per_wg, hw
     if hw:
         B = M // hw
         sws = torch.full((ctx.gn_stats_floats(B, n_pad),), float("nan"), device=DEV)
@@ -477,18 +490,33 @@ def test_mlp_tail_against_fp64(ctx, name, s):
     assert ctx.lib.upk_geglu_mlp_supported(ctx.h, C.byref(d))
     ctx._chk(ctx.lib.upk_geglu_mlp_f16(ctx.h, C.byref(d), ctx._s()))
     torch.cuda.synchronize()
+    if not hw:
+        return y.cpu(), None
+    return y.cpu(), sws[: B * (hw // rows) * 2 * n_pad].reshape(B, hw // rows, 2, n_pad).cpu()
+
+
+def check_mlp_tail(o, y, part, what, s):
+    """y against mlp_case_ref, and the GroupNorm partials against the fp64 sums of y."""
+    M, rows, hw, c = o["M"], o["rows"], o["hw"], o["c"]
     ref, bound = R.mlp_case_ref(o)
     assert float(ref.abs().max()) < 6e4
-    assert report("mlp tail %s" % name, s, R.ratio(y.cpu(), ref, bound)) <= 1
+    assert report(what, s, R.ratio(y, ref, bound)) <= 1
     if hw:
         # the GroupNorm partials it leaves: per (row block, channel) fp32 sums of its OWN fp16 output, n = rows terms
         # each, so off from the fp64 sums by at most n e32 sum|y| (n e32 sum y^2, plus e32 per square)
-        nblk = hw // rows
-        part = sws[: B * nblk * 2 * n_pad].reshape(B, nblk, 2, n_pad).cpu().to(F64)
-        yb = y.cpu().to(F64).reshape(B, nblk, rows, c)
+        B, nblk = M // hw, hw // rows
+        part = part.to(F64)
+        yb = y.to(F64).reshape(B, nblk, rows, c)
         r1 = R.ratio(part[:, :, 0, :c], yb.sum(2), rows * R.E32H * yb.abs().sum(2))
         r2 = R.ratio(part[:, :, 1, :c], (yb * yb).sum(2), (rows + 1) * R.E32H * (yb * yb).sum(2))
-        assert report("mlp tail %s GroupNorm partials" % name, s, max(r1, r2)) <= 1
+        assert report(what + " GroupNorm partials", s, max(r1, r2)) <= 1
+
+
+@pytest.mark.parametrize("s", R.SCALES)
+@pytest.mark.parametrize("name", list(R.MLP_CASES))
+def test_mlp_tail_against_fp64(ctx, name, s):
+    o = R.mlp_case(name, s)
+    check_mlp_tail(o, *launch_mlp_tail(ctx, o), "mlp tail %s" % name, s)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
