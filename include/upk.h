@@ -1027,6 +1027,46 @@ int upk_probe_placement(upk_ctx* ctx, uint32_t* out_dev, int nblocks, int spin_c
 int upk_probe_clock(upk_ctx* ctx, unsigned long long* out_dev, long long spin_wall_ticks, upk_stream stream);
 
 /* ------------------------------------------------------------------ */
+/* Keyed device noise: Philox4x32-10 normals as a pure function of     */
+/* (key, element, row, stream, draw).                                   */
+/* ------------------------------------------------------------------ */
+/* upk_randn_keyed_f32 fills the noise tables the sampler step kernels read (and x_T) without a generator state: one
+ * launch, no allocation, no host state, no synchronisation; graph-capturable; counted in class "other".
+ *
+ * Generator: Philox4x32-10 (Salmon et al., SC'11) with the Random123 constants: multipliers M0 = 0xD2511F53, M1 =
+ * 0xCD9E8D57, Weyl key increments 0x9E3779B9 (k0) and 0xBB67AE85 (k1).  One round: hi0:lo0 = M0 * c0, hi1:lo1 = M1 * c2
+ * (32 x 32 -> 64 bit), c <- {hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0}, then k0 += 0x9E3779B9, k1 += 0xBB67AE85; ten rounds.
+ *   key      (k0, k1) = keys[2 b], keys[2 b + 1] of sample b: uint32 [batch, 2] on the device
+ *   counter  (c0, c1, c2, c3) = (q, row, stream_id, draw): q = e >> 2 for element e of the sample's n elements (n <= 2^34),
+ *            row = the ABSOLUTE row of the table (row0 + r for the r-th row written), stream_id = the use the caller
+ *            separates (x_T, step noise, q_sample noise, ...), draw = the sampling call among calls that share keys
+ * The four output words (w0, w1, w2, w3) of that call belong to elements 4 q .. 4 q + 3; with n % 4 != 0 the words past
+ * element n - 1 are discarded.  upk_philox_u32 writes word e & 3 for element e.
+ * Normals (Box-Muller on the word pairs (w0, w1) -> elements 4 q, 4 q + 1 and (w2, w3) -> elements 4 q + 2, 4 q + 3):
+ *   u1 = ((w_a >> 8) + 1) * 2^-24    in (0, 1], exact in fp32
+ *   u2 = (w_b >> 8) * 2^-24          in [0, 1), exact in fp32
+ *   r = sqrt(-2 ln u1);  z_a = r cos(2 pi u2),  z_b = r sin(2 pi u2)
+ * evaluated in fp32 (log, one multiplication, a correctly rounded sqrt, cos / sin of pi * (2 u2) with 2 u2 exact, one
+ * multiplication each; no FMA contraction): within 1e-5 of the fp64 value of the same formula, |z| <= sqrt(48 ln 2) < 5.77.
+ * Layout: element e of sample b of row r (row0 <= r < row0 + rows) is
+ *   out[(r - row0) * batch * n + b * n + e] = fl(z * row_scale[r])      (row_scale == NULL: z)
+ * the layout of the [rows, batch * n] step-noise tables and, with rows == 1, of a dense [batch, C, H, W] latent.  row_scale
+ * is a device fp32 table indexed by the absolute row (at least row0 + rows entries); a row whose scale is 0 is written
+ * as +0.  A value depends on nothing but (key, e, row, stream_id, draw) and the row's scale: not on batch, on the sample's
+ * position in the batch, on the [row0, row0 + rows) window, on the alignment of out or on the launch geometry.  Stores are
+ * 16 bytes wide wherever four consecutive elements of a sample fill an aligned group of out (out + b * n need not be aligned:
+ * heads and tails go element by element).
+ * Errors: UPK_EINVAL for null keys / out, non-positive batch, n or rows, negative row0 (or row0 + rows above 2^31 - 1),
+ * n above 2^34, a pointer not 4-byte aligned; UPK_ESHAPE for a table of 2^62 elements or more. */
+int upk_randn_keyed_f32(upk_ctx* ctx, const uint32_t* keys, int batch, long long n, int row0, int rows, uint32_t stream_id,
+                        uint32_t draw, const float* row_scale, float* out, upk_stream stream);
+/* The raw Philox word of every element, same layout, same device function as the normals (the integer stage, exactly
+ * testable): out[(r - row0) * batch * n + b * n + e] = w[e & 3] of the call with counter (e >> 2, r, stream_id, draw).
+ * Errors as above. */
+int upk_philox_u32(upk_ctx* ctx, const uint32_t* keys, int batch, long long n, int row0, int rows, uint32_t stream_id,
+                   uint32_t draw, uint32_t* out, upk_stream stream);
+
+/* ------------------------------------------------------------------ */
 /* HIP graph helpers (the 50-step loop replays one captured step).      */
 /* ------------------------------------------------------------------ */
 typedef struct upk_graph upk_graph;

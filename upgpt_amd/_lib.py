@@ -33,6 +33,7 @@ SYMBOLS = [
     "upk_lpips_input_f16", "upk_relu_pool_nhwc_f16", "upk_lpips_ws_bytes", "upk_lpips_layer_f16",
     "upk_conv2d_rect_f16", "upk_pool3_nhwc_f16", "upk_fid_input_f16", "upk_avgpool_global_f32",
     "upk_q_sample_f32", "upk_p_losses_ws_bytes", "upk_p_losses_f32",
+    "upk_randn_keyed_f32", "upk_philox_u32",
     "upk_advance_step", "upk_step_autoadvance", "upk_kernel_launches", "upk_graph_begin", "upk_graph_end", "upk_graph_launch", "upk_graph_destroy",
     "upk_prof_enable", "upk_prof_collect",
     "upk_stream_create_cumask", "upk_stream_destroy", "upk_probe_placement", "upk_probe_clock",
@@ -223,6 +224,8 @@ def load_library(path=None):
             "upk_p_losses_ws_bytes": (C.c_size_t, [i32, i32, i32]),
             "upk_p_losses_f32": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32, vp, i32, i32, i32, vp,
                                            C.c_size_t, vp]),
+            "upk_randn_keyed_f32": (C.c_int, [vp, vp, i32, i64, i32, i32, C.c_uint32, C.c_uint32, vp, vp, vp]),
+            "upk_philox_u32": (C.c_int, [vp, vp, i32, i64, i32, i32, C.c_uint32, C.c_uint32, vp, vp]),
             "upk_advance_step": (C.c_int, [vp, vp, vp]),
             "upk_step_autoadvance": (C.c_int, [vp, vp]),
             "upk_kernel_launches": (C.c_longlong, [vp, i32]),
@@ -522,6 +525,16 @@ class Context:
                                             _ptr(logvar), _ptr(lvlb_weights), int(n_t), int(loss_type), float(l_simple_weight),
                                             float(original_elbo_weight), _ptr(out), int(batch), int(c), int(hw), _ptr(ws),
                                             int(ws_bytes), self._s()))
+
+    def randn_keyed(self, keys, batch, n, row0, rows, stream_id, draw, row_scale, out):
+        """upk_randn_keyed_f32: out [rows, batch, n] fp32 <- keyed normals * row_scale[absolute row] (None: unscaled)."""
+        self._chk(self.lib.upk_randn_keyed_f32(self.h, _ptr(keys), int(batch), int(n), int(row0), int(rows), int(stream_id),
+                                               int(draw), _ptr(row_scale), _ptr(out), self._s()))
+
+    def philox_u32(self, keys, batch, n, row0, rows, stream_id, draw, out):
+        """upk_philox_u32: out [rows, batch, n] <- the raw Philox word of every element (32-bit storage)."""
+        self._chk(self.lib.upk_philox_u32(self.h, _ptr(keys), int(batch), int(n), int(row0), int(rows), int(stream_id),
+                                          int(draw), _ptr(out), self._s()))
 
     def step_autoadvance(self, done):
         """Arms (done: zeroed device int32) or disarms (None) the step kernels' own increment of *step."""

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import ddim as _ddim
+from . import rng
 from ._check import require
 from ._lib import DDPM_CLIP, DDPM_X0, get_context, host_io
 from .ddim import noise_like
@@ -75,11 +76,19 @@ class AncestralSampling:
     @torch.no_grad()
     def p_sample(self, x, c, t, clip_denoised=False, repeat_noise=False, return_codebook_ids=False,
                  quantize_denoised=False, return_x0=False, temperature=1., noise_dropout=0., score_corrector=None,
-                 corrector_kwargs=None, noise=None):
+                 corrector_kwargs=None, noise=None, noise_keys=None):
         """ddpm.py:1157-1187.  `noise` (an extension): the standard normals of this step instead of a draw.  With one
-        t for the whole batch the update is one upk_ddpm_step_f32 launch; per-sample t go through torch."""
+        t for the whole batch the update is one upk_ddpm_step_f32 launch; per-sample t go through torch.
+        noise_keys (without `noise`; one t for the batch): the keyed normals of the step at timestep t, row
+        num_timesteps - 1 - t of rng.STREAM_STEP — the row the full chain uses for it."""
+        require(noise_keys is None or not repeat_noise,
+                "repeat_noise shares one draw over the batch; noise_keys gives every sample its own", ValueError)
         self._no_quantize(quantize_denoised, return_codebook_ids)
         b = x.shape[0]
+        if noise is None and noise_keys is not None:
+            rng.check_keys(noise_keys, b)
+            require(bool((t == t[0]).all()), "noise_keys needs one timestep for the whole batch", ValueError)
+            noise = rng.randn(noise_keys, tuple(x.shape), rng.STREAM_STEP, row0=self.num_timesteps - 1 - int(t[0]))
         if bool((t == t[0]).all()):
             model_out = self._model_out(x, c, t, score_corrector, corrector_kwargs)
             if noise is None:
@@ -112,8 +121,9 @@ class AncestralSampling:
     def progressive_denoising(self, cond, shape, verbose=True, callback=None, quantize_denoised=False,
                               img_callback=None, mask=None, x0=None, temperature=1., noise_dropout=0.,
                               score_corrector=None, corrector_kwargs=None, batch_size=None, x_T=None, start_T=None,
-                              log_every_t=None, normals_sequence=None):
-        """ddpm.py:1189-1244 -> (x, [x0_partial at the logged steps])."""
+                              log_every_t=None, normals_sequence=None, noise_keys=None):
+        """ddpm.py:1189-1244 -> (x, [x0_partial at the logged steps]).  noise_keys: see p_sample_loop."""
+        rng.check_keys(noise_keys, shape[0] if batch_size is None else batch_size, normals_sequence)
         if not log_every_t:
             log_every_t = self.log_every_t
         if batch_size is not None:
@@ -124,13 +134,17 @@ class AncestralSampling:
         T = self.num_timesteps if start_T is None else min(self.num_timesteps, start_T)
         return self._ancestral(cond, tuple(shape), x_T, T, temperature, mask, x0, normals_sequence, callback,
                                img_callback, log_every_t, True, quantize_denoised, noise_dropout, score_corrector,
-                               corrector_kwargs)
+                               corrector_kwargs, noise_keys)
 
     @torch.no_grad()
     def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None,
                       timesteps=None, quantize_denoised=False, mask=None, x0=None, img_callback=None, start_T=None,
-                      log_every_t=None, normals_sequence=None):
-        """ddpm.py:1246-1291 -> x, or (x, [x_T] + [x at the logged steps])."""
+                      log_every_t=None, normals_sequence=None, noise_keys=None):
+        """ddpm.py:1246-1291 -> x, or (x, [x_T] + [x at the logged steps]).
+        noise_keys (upgpt_amd.rng.NoiseKeys, one key per sample): x_T when not given (rng.STREAM_XT, row 0), the
+        posterior noise of loop position k (STREAM_STEP, row k) and a mask's q_sample noise (STREAM_QSAMPLE, row k) are
+        keyed normals; the torch generator is neither read nor advanced.  Not combinable with normals_sequence."""
+        rng.check_keys(noise_keys, shape[0], normals_sequence)
         if not log_every_t:
             log_every_t = self.log_every_t
         T = self.num_timesteps if timesteps is None else timesteps
@@ -140,19 +154,21 @@ class AncestralSampling:
             require(x0 is not None, "mask given without x0", AssertionError)
             require(x0.shape[2:3] == mask.shape[2:3], "spatial size has to match", AssertionError)
         img, inter = self._ancestral(cond, tuple(shape), x_T, T, 1., mask, x0, normals_sequence, callback,
-                                     img_callback, log_every_t, False, quantize_denoised, 0., None, None)
+                                     img_callback, log_every_t, False, quantize_denoised, 0., None, None, noise_keys)
         return (img, inter) if return_intermediates else img
 
     @torch.no_grad()
     def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, verbose=True, timesteps=None,
                quantize_denoised=False, mask=None, x0=None, shape=None, normals_sequence=None, **kwargs):
         """ddpm.py:1293-1310.  Like the reference, every other keyword (eta, unconditional_guidance_*, callbacks that
-        log_images forwards) is dropped."""
+        log_images forwards) is dropped — except `noise_keys` (p_sample_loop)."""
+        noise_keys = kwargs.get("noise_keys")
+        rng.check_keys(noise_keys, batch_size, normals_sequence)
         if shape is None:
             shape = (batch_size, self.channels, *self.image_size)
         return self.p_sample_loop(_slice_cond(cond, batch_size), shape, return_intermediates=return_intermediates,
                                   x_T=x_T, verbose=verbose, timesteps=timesteps, quantize_denoised=quantize_denoised,
-                                  mask=mask, x0=x0, normals_sequence=normals_sequence)
+                                  mask=mask, x0=x0, normals_sequence=normals_sequence, noise_keys=noise_keys)
 
     # ---- the chain
     @staticmethod
@@ -175,7 +191,8 @@ class AncestralSampling:
                 and self.device.type == "cuda")
 
     def _ancestral(self, cond, shape, x_T, T, temperature, mask, x0, normals_sequence, callback, img_callback,
-                   log_every_t, log_x0, quantize_denoised, noise_dropout, score_corrector, corrector_kwargs):
+                   log_every_t, log_x0, quantize_denoised, noise_dropout, score_corrector, corrector_kwargs,
+                   noise_keys=None):
         """The loop of p_sample_loop (log_x0=False: intermediates [x_T] + x) and progressive_denoising (log_x0=True:
         intermediates x0_partial).  Timesteps T-1 ... 0."""
         self._no_quantize(quantize_denoised)
@@ -189,20 +206,30 @@ class AncestralSampling:
         ns = self._normals(normals_sequence, T, masked, shape)
         if self._fast_ok(cond, quantize_denoised, noise_dropout, score_corrector):
             return self._fast_chain(cond, shape, x_T, T, temps, mask, x0, ns, callback, img_callback, log_every_t,
-                                    log_x0)
+                                    log_x0, noise_keys)
         device = self.betas.device
         b = shape[0]
-        img = torch.randn(shape, device=device) if x_T is None else x_T
+        keyed = noise_keys is not None
+        if x_T is not None:
+            img = x_T
+        else:
+            img = rng.randn(noise_keys, shape, rng.STREAM_XT) if keyed else torch.randn(shape, device=device)
         intermediates = [] if log_x0 else [img]
         for k, i in enumerate(reversed(range(0, T))):
             ts = torch.full((b,), i, device=device, dtype=torch.long)
             nz = None if ns is None else ns[(2 if masked else 1) * k]
+            if keyed:
+                nz = rng.randn(noise_keys, shape, rng.STREAM_STEP, row0=k)
             img, x0_partial = self.p_sample(img, cond, ts, clip_denoised=self.clip_denoised, return_x0=True,
                                             temperature=temps[i], noise_dropout=noise_dropout,
                                             score_corrector=score_corrector, corrector_kwargs=corrector_kwargs,
                                             noise=nz)
             if masked:
-                img_orig = self.q_sample(x0, ts, noise=None if ns is None else ns[2 * k + 1].to(device))
+                if keyed:
+                    nq = rng.randn(noise_keys, shape, rng.STREAM_QSAMPLE, row0=k)
+                else:
+                    nq = None if ns is None else ns[2 * k + 1].to(device)
+                img_orig = self.q_sample(x0, ts, noise=nq)
                 img = img_orig * mask + (1. - mask) * img
             if i % log_every_t == 0 or i == T - 1:
                 intermediates.append(x0_partial if log_x0 else img)
@@ -212,13 +239,15 @@ class AncestralSampling:
                 img_callback(img, i)
         return img, intermediates
 
-    def _fast_chain(self, cond, shape, x_T, T, temps, mask, x0, ns, callback, img_callback, log_every_t, log_x0):
+    def _fast_chain(self, cond, shape, x_T, T, temps, mask, x0, ns, callback, img_callback, log_every_t, log_x0,
+                    noise_keys=None):
         unet = self.model.diffusion_model
         b, C, H, W = shape
         c_concat, c_cross = self._split_cond(cond)
         plan = unet.plan(b, H, W, c_cross.shape[1], T, "sampler")
         dev = plan.dev
         masked = mask is not None
+        keyed = noise_keys is not None
         with torch.cuda.device(dev):
             st = getattr(plan, "_ddpm_state", None)
             if st is None:
@@ -229,9 +258,13 @@ class AncestralSampling:
             order = np.arange(T)[::-1].copy()  # loop order: timesteps T-1 ... 0 (no +1 as in DDIM)
             rkey = ("ddpm", order.astype(np.float32).tobytes())
             # every call draws (or copies in) T rows of noise, so it always takes the upload lock, as DDIM does whenever
-            # it has noise to draw (_lib.host_io)
+            # it has noise to draw (_lib.host_io).  (Keyed noise needs no lock, but this call uploads its coefficient and
+            # temperature tables every time, so it keeps it.)
             with host_io():
-                img = torch.randn(shape, device=dev) if x_T is None else x_T.to(dev, torch.float32)
+                if x_T is not None:
+                    img = x_T.to(dev, torch.float32)
+                else:
+                    img = rng.randn(noise_keys, shape, rng.STREAM_XT) if keyed else torch.randn(shape, device=dev)
                 st.x.copy_(img)
                 plan.load_sampler_inputs(st.x, c_concat, c_cross, unet.in_channels, rkey, order.astype(np.float32))
                 st.coefs.copy_(ddpm_coefficient_table(self, order))
@@ -244,7 +277,13 @@ class AncestralSampling:
                     x0d = x0.to(dev, torch.float32)
                     sx0.copy_(x0d.expand(shape).reshape(-1))
                     smask.copy_(mask.to(dev, torch.float32).expand(shape).reshape(-1))
-                for k in range(T):
+                tv = torch.as_tensor([float(temps[i]) for i in order], dtype=torch.float32)
+                if keyed:  # one launch per table; noise_like(...) * temperature[i] is the launch's row scale
+                    rng.randn(noise_keys, shape, rng.STREAM_STEP, rows=T, out=nz,
+                              scale=tv.to(dev) if bool((tv != 1.).any()) else None)
+                    if masked:
+                        rng.randn(noise_keys, shape, rng.STREAM_QSAMPLE, rows=T, out=nz2)
+                for k in ([] if keyed else range(T)):
                     if ns is not None:
                         nz[k].copy_(ns[2 * k if masked else k].to(dev, torch.float32).reshape(-1))
                         if masked:
@@ -254,8 +293,7 @@ class AncestralSampling:
                         if masked:
                             nz2[k].copy_(torch.randn_like(x0d).expand(shape).reshape(-1))
                 # noise_like(...) * temperature[i] (ddpm.py:1174), i = T-1-k
-                tv = torch.as_tensor([float(temps[i]) for i in order], dtype=torch.float32)
-                if bool((tv != 1.).any()):
+                if not keyed and bool((tv != 1.).any()):
                     nz.mul_(tv.to(dev)[:, None])
                 plan.step.zero_()
                 plan.prep.run()

@@ -19,6 +19,7 @@ import os
 import numpy as np
 import torch
 
+from . import rng
 from ._check import require
 from ._lib import host_io
 from .schedule import (ddim_coefficient_table, extract_into_tensor, make_ddim_sampling_parameters,
@@ -84,7 +85,14 @@ class DDIMSampler(object):
                unconditional_guidance_scale=1., unconditional_conditioning=None, **kwargs):
         """`normals_sequence` (unused by the reference) is honoured here as an injected noise
         source: a [S, B, C, H, W] tensor (or list) of standard normals in loop order, for
-        device-independent eta > 0 runs."""
+        device-independent eta > 0 runs.
+        `noise_keys=` (through **kwargs; an upgpt_amd.rng.NoiseKeys of batch_size keys): every normal of the call is a
+        function of (key of the sample, draw, stream, loop position, element) — x_T when not given (STREAM_XT, row 0), the
+        step noise of loop position i (STREAM_STEP, row i) and, with a mask, q_sample's noise of position i
+        (STREAM_QSAMPLE, row i).  The torch generator is neither read nor advanced: "the generator advances by S draws"
+        (below) holds only WITHOUT keys.  Not combinable with normals_sequence (ValueError)."""
+        noise_keys = kwargs.get("noise_keys")
+        rng.check_keys(noise_keys, batch_size, normals_sequence)
         if conditioning is not None:
             first = conditioning[list(conditioning.keys())[0]] if isinstance(conditioning, dict) else conditioning
             cbs = (first[0] if isinstance(first, (list, tuple)) else first).shape[0]
@@ -107,7 +115,7 @@ class DDIMSampler(object):
                                   score_corrector=score_corrector, corrector_kwargs=corrector_kwargs, x_T=x_T,
                                   log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning,
-                                  normals_sequence=normals_sequence)
+                                  normals_sequence=normals_sequence, noise_keys=noise_keys)
 
     # ------------------------------------------------------------------ fast path
     def _fast_ok(self, cond, ddim_use_original_steps, quantize_denoised, mask, noise_dropout, score_corrector,
@@ -125,15 +133,20 @@ class DDIMSampler(object):
         return 0 < n <= len(self.ddim_timesteps) and np.array_equal(timesteps, self.ddim_timesteps[:n])
 
     def _fast_sampling(self, cond, shape, x_T, timesteps, callback, img_callback, log_every_t, temperature,
-                       normals_sequence, cfg_scale=1., uc=None, mask=None, x0=None, edit=False):
+                       normals_sequence, cfg_scale=1., uc=None, mask=None, x0=None, edit=False, noise_keys=None):
         """`timesteps`: the schedule, or a prefix of it (decode, ddim_sampling(timesteps=)): T = len(timesteps) steps
         from row S - T of the S-row tables.  mask / x0: inpainting (ddim.py:144-147).  The reference blends
         q_sample(x0, t) into the latent BEFORE the model evaluation of every step; in the captured loop the step kernel
         does it for the NEXT step (the first one is blended here), reading row r of the `keep` table = q_sample(x0, t_r),
         which is filled before the loop by one model.q_sample call per step — each followed by that step's noise draw,
         so the generator sees the general path's order of draws and an overridden q_sample keeps working.
-        edit: run upk_ddim_step_edit_f32 also without a mask and from row 0.  log_every_t None: nothing is logged."""
+        edit: run upk_ddim_step_edit_f32 also without a mask and from row 0.  log_every_t None: nothing is logged.
+        noise_keys: x_T, rows k .. S-1 of the noise table (scaled by sigma_i * temperature inside the launch) and the
+        q_sample noise of the keep rows come from upk_randn_keyed_f32 — one launch each on this lane's stream, no
+        torch.randn, no generator state; such a call takes host_io() only for what it uploads (a fresh schedule, host
+        inputs), never for its noise."""
         masked = mask is not None
+        keyed = noise_keys is not None
         require(not masked or x0 is not None, "mask given without x0", ValueError)
         model = self.model
         unet = model.model.diffusion_model
@@ -166,12 +179,18 @@ class DDIMSampler(object):
             ckey = (f64b(self.ddim_alphas), f64b(self.ddim_alphas_prev), f64b(self.ddim_sigmas))
             fresh_rows = getattr(plan, "_t_rows_key", None) != rkey
             fresh_coefs = getattr(st, "_coef_key", None) != ckey
-            fresh = fresh_rows or fresh_coefs
+            # (keyed: the per-row scale sigma_i * temperature lives on the device next to the coefficients)
+            skey = (ckey, float(temperature))
+            fresh_scale = keyed and with_noise and getattr(st, "_nscale_key", None) != skey
+            fresh = fresh_rows or fresh_coefs or fresh_scale
             on_host = any(t is not None and torch.is_tensor(t) and not t.is_cuda for t in (x_T, c_concat, c_cross, mask, x0))
             # uploads from the host never overlap another lane's graph capture (_lib.host_io); a call with everything on
             # the device and an unchanged schedule uploads nothing and takes no lock
-            with (host_io() if (fresh or on_host or with_noise) else contextlib.nullcontext()):
-                img = torch.randn(shape, device=dev) if x_T is None else x_T.to(dev, torch.float32)
+            with (host_io() if (fresh or on_host or (with_noise and not keyed)) else contextlib.nullcontext()):
+                if x_T is not None:
+                    img = x_T.to(dev, torch.float32)
+                else:
+                    img = rng.randn(noise_keys, shape, rng.STREAM_XT) if keyed else torch.randn(shape, device=dev)
                 st.x.copy_(img)
                 if masked:
                     keep, emask, _ = st.ensure_edit()
@@ -192,16 +211,25 @@ class DDIMSampler(object):
                 if with_noise and normals_sequence is not None:
                     ns = normals_sequence if torch.is_tensor(normals_sequence) else torch.stack(list(normals_sequence))
                     nz[k:].copy_(ns.to(dev, torch.float32).reshape(T, -1))
+                if keyed:
+                    if fresh_scale:
+                        st._nscale = (sig * float(temperature)).to(dev)  # indexed by the absolute row
+                        st._nscale_key = skey
+                    if with_noise:
+                        rng.randn(noise_keys, shape, rng.STREAM_STEP, row0=k, rows=T, scale=st._nscale, out=nz[k:])
+                    if masked:  # the q_sample noise of every keep row in one launch, then q_sample row by row in place
+                        rng.randn(noise_keys, shape, rng.STREAM_QSAMPLE, row0=k, rows=T, out=keep[k:])
                 for i in range(k, S):
                     if masked:
                         ts = torch.full((b,), int(desc[i]), device=dev, dtype=torch.long)
-                        keep[i].copy_(model.q_sample(x0, ts).to(dev, torch.float32).reshape(-1))
-                    if normals_sequence is None:
+                        qn = {"noise": keep[i].view(shape)} if keyed else {}
+                        keep[i].copy_(model.q_sample(x0, ts, **qn).to(dev, torch.float32).reshape(-1))
+                    if normals_sequence is None and not keyed:
                         if with_noise:
                             nz[i].copy_(torch.randn(shape, device=dev).reshape(-1))
                         else:
                             torch.randn(shape, device=dev)  # (sigma = 0: the draw is discarded, as in the reference)
-                if with_noise:
+                if with_noise and not keyed:
                     nz[k:].mul_((sig[k:] * float(temperature)).to(dev)[:, None])
                 first = st.x.clone()  # (the reference's intermediates start with the unblended x_T)
                 if masked:  # the blend in front of the first step; the step kernel does the later ones
@@ -238,7 +266,12 @@ class DDIMSampler(object):
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
-                      unconditional_guidance_scale=1., unconditional_conditioning=None, normals_sequence=None):
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, normals_sequence=None,
+                      noise_keys=None):
+        """noise_keys: see sample().  The step-by-step path draws the same keyed normals one row per launch, so a keyed
+        run is the same chain on either path."""
+        rng.check_keys(noise_keys, shape[0], normals_sequence)
+        keyed = noise_keys is not None
         device = self.model.betas.device
         b = shape[0]
         if timesteps is None:
@@ -252,24 +285,32 @@ class DDIMSampler(object):
                 and self._is_tail(timesteps):
             return self._fast_sampling(cond, shape, x_T, timesteps, callback, img_callback, log_every_t,
                                        temperature, normals_sequence, cfg_scale=unconditional_guidance_scale,
-                                       uc=unconditional_conditioning, mask=mask, x0=x0)
+                                       uc=unconditional_conditioning, mask=mask, x0=x0, noise_keys=noise_keys)
 
         # general path: one apply_model + one fused update kernel per step, driven from Python
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device)
+        if x_T is not None:
+            img = x_T.to(device)
+        else:
+            img = rng.randn(noise_keys, shape, rng.STREAM_XT) if keyed else torch.randn(shape, device=device)
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         time_range = reversed(range(0, timesteps)) if ddim_use_original_steps else np.flip(timesteps)
         total_steps = timesteps if ddim_use_original_steps else timesteps.shape[0]
         print(f"Running DDIM Sampling with {total_steps} timesteps")
+        # absolute row of loop position i: a shortened chain runs the LAST total_steps rows of the full table
+        row_of = (self.ddpm_num_timesteps if ddim_use_original_steps else int(self.ddim_timesteps.shape[0])) - total_steps
         for i, step in enumerate(time_range):
             index = total_steps - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
             if mask is not None:
                 require(x0 is not None, "mask given without x0", ValueError)
-                img_orig = self.model.q_sample(x0, ts)
+                qn = {"noise": rng.randn(noise_keys, shape, rng.STREAM_QSAMPLE, row0=row_of + i)} if keyed else {}
+                img_orig = self.model.q_sample(x0, ts, **qn)
                 img = img_orig * mask + (1. - mask) * img
             noise = None
             if normals_sequence is not None:
                 noise = normals_sequence[i].to(device)
+            elif keyed:
+                noise = rng.randn(noise_keys, shape, rng.STREAM_STEP, row0=row_of + i)
             img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, use_original_steps=ddim_use_original_steps,
                                               quantize_denoised=quantize_denoised, temperature=temperature,
                                               noise_dropout=noise_dropout, score_corrector=score_corrector,
@@ -302,7 +343,9 @@ class DDIMSampler(object):
     @torch.no_grad()
     def p_sample_ddim(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
-                      unconditional_guidance_scale=1., unconditional_conditioning=None, noise=None):
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, noise=None, noise_keys=None):
+        require(noise_keys is None or not repeat_noise,
+                "repeat_noise shares one draw over the batch; noise_keys gives every sample its own", ValueError)
         b, device = x.shape[0], x.device
         if unconditional_conditioning is None or unconditional_guidance_scale == 1.:
             e_t = self.model.apply_model(x, t, c)
@@ -319,12 +362,20 @@ class DDIMSampler(object):
         if quantize_denoised:
             raise NotImplementedError("quantize_denoised needs a VQ first stage (not on the UPGPT path)")
         return self._ddim_update(x, e_t, index, use_original_steps=use_original_steps, temperature=temperature,
-                                 noise_dropout=noise_dropout, repeat_noise=repeat_noise, noise=noise)
+                                 noise_dropout=noise_dropout, repeat_noise=repeat_noise, noise=noise,
+                                 noise_keys=noise_keys)
 
     def _ddim_update(self, x, e_t, index, use_original_steps=False, temperature=1., noise_dropout=0.,
-                     repeat_noise=False, noise=None):
-        """(x_prev, pred_x0) of ddim.py:189-203 for DDIM index `index`, in upk_ddim_step_f32."""
+                     repeat_noise=False, noise=None, noise_keys=None):
+        """(x_prev, pred_x0) of ddim.py:189-203 for DDIM index `index`, in upk_ddim_step_f32.  noise_keys (without
+        `noise`): this step's normals are the keyed row of the index' loop position (rng.STREAM_STEP)."""
+        require(noise_keys is None or not repeat_noise,
+                "repeat_noise shares one draw over the batch; noise_keys gives every sample its own", ValueError)
         b, device = x.shape[0], x.device
+        if noise is None and noise_keys is not None:
+            rng.check_keys(noise_keys, b)
+            n_rows = self.ddpm_num_timesteps if use_original_steps else int(self.ddim_timesteps.shape[0])
+            noise = rng.randn(noise_keys, tuple(x.shape), rng.STREAM_STEP, row0=n_rows - 1 - int(index))
         if use_original_steps:
             alphas, alphas_prev = self.model.alphas_cumprod, self.model.alphas_cumprod_prev
             sqrt_1m, sigmas = self.model.sqrt_one_minus_alphas_cumprod, self.ddim_sigmas_for_original_num_steps
@@ -368,7 +419,9 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               use_original_steps=False):
+               use_original_steps=False, noise_keys=None):
+        """noise_keys: the step noise of the chain's rows (rng.STREAM_STEP), instead of one generator draw per step."""
+        rng.check_keys(noise_keys, x_latent.shape[0])
         timesteps = np.arange(self.ddpm_num_timesteps) if use_original_steps else self.ddim_timesteps
         timesteps = timesteps[:t_start]
         total_steps = timesteps.shape[0]
@@ -377,7 +430,7 @@ class DDIMSampler(object):
             # the last total_steps rows of the captured loop; one generator draw per step, as p_sample_ddim makes
             return self._fast_sampling(cond, tuple(x_latent.shape), x_latent, timesteps, None, None, None, 1., None,
                                        cfg_scale=unconditional_guidance_scale, uc=unconditional_conditioning,
-                                       edit=True)[0]
+                                       edit=True, noise_keys=noise_keys)[0]
         print(f"Running DDIM Sampling with {total_steps} timesteps")
         x_dec = x_latent
         for i, step in enumerate(np.flip(timesteps)):
@@ -385,5 +438,6 @@ class DDIMSampler(object):
             ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
             x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index, use_original_steps=use_original_steps,
                                           unconditional_guidance_scale=unconditional_guidance_scale,
-                                          unconditional_conditioning=unconditional_conditioning)
+                                          unconditional_conditioning=unconditional_conditioning,
+                                          noise_keys=noise_keys)
         return x_dec

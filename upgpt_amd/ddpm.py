@@ -368,12 +368,13 @@ class LatentDiffusion(AncestralSampling, DDPM):
         raise NotImplementedError("fused sampler path for conditioning_key=%r" % key)
 
     # ---- first stage
-    def get_first_stage_encoding(self, encoder_posterior):
-        """ddpm.py:566-575: a posterior is sampled, a tensor is taken as is; both scaled by scale_factor."""
+    def get_first_stage_encoding(self, encoder_posterior, noise=None):
+        """ddpm.py:566-575: a posterior is sampled, a tensor is taken as is; both scaled by scale_factor.  `noise` (an
+        extension): the standard normals of the posterior sample instead of a generator draw."""
         if torch.is_tensor(encoder_posterior):
             z = encoder_posterior
         elif callable(getattr(encoder_posterior, "sample", None)):
-            z = encoder_posterior.sample()
+            z = encoder_posterior.sample() if noise is None else encoder_posterior.sample(noise)
         else:
             raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
         return self.scale_factor * z
@@ -429,16 +430,24 @@ class LatentDiffusion(AncestralSampling, DDPM):
         return (c if bs is None else c[:bs]), xc
 
     def get_input(self, batch, k, return_first_stage_outputs=False, force_c_encode=False, cond_key=None,
-                  return_original_cond=False, bs=None, return_loss_w=False, encode_image=True):
+                  return_original_cond=False, bs=None, return_loss_w=False, encode_image=True, noise_keys=None):
         """ddpm.py:684-769 -> [z, {'c_crossattn': c, 'c_concat': [mask]}, (x, xrec)?, (xc)?, (loss_w)?].
-        The image is encoded only when an encoder is available."""
+        The image is encoded only when an encoder is available.
+        noise_keys (upgpt_amd.rng.NoiseKeys, in batch order, at least as many as samples are taken): the posterior sample
+        behind z (and with it the reconstruction) is the keyed draw rng.STREAM_POSTERIOR instead of the generator's."""
         dev = self.device
         head = (lambda v: v) if bs is None else (lambda v: v[:bs])
         x = head(DDPM.get_input(self, batch, k)).to(dev)
         z = None
         if encode_image:
             try:
-                z = self.get_first_stage_encoding(self.encode_first_stage(x)).detach()
+                post = self.encode_first_stage(x)
+                if noise_keys is not None and callable(getattr(post, "sample", None)):
+                    from . import rng
+                    nz = rng.randn(noise_keys[:x.shape[0]], tuple(post.mean.shape), rng.STREAM_POSTERIOR)
+                    z = self.get_first_stage_encoding(post, noise=nz).detach()
+                else:
+                    z = self.get_first_stage_encoding(post).detach()
             except NotImplementedError:
                 pass
         c = xc = mask = None
@@ -570,15 +579,23 @@ class LatentDiffusion(AncestralSampling, DDPM):
     @torch.no_grad()
     def log_images(self, batch, N=8, n_row=4, sample=True, ddim_steps=200, ddim_eta=1., return_keys=None,
                    quantize_denoised=False, inpaint=False, plot_denoise_rows=False, plot_progressive_rows=False,
-                   plot_diffusion_rows=False, seed=None, **kwargs):
+                   plot_diffusion_rows=False, seed=None, noise_keys=None, **kwargs):
         """ddpm.py:1380-1499 — the path InferenceModel.generate drives (generate_utils.py:159-169): conditioning
         assembly -> EMA scope -> DDIM (ddim_steps=None: the DDPM chain) -> decode, and the reference's plotting rows.
-        Returns {'reconstruction'?, 'samples', ...}."""
+        Returns {'reconstruction'?, 'samples', ...}.
+        noise_keys (upgpt_amd.rng.NoiseKeys, one key per sample of the batch, in batch order): every sampling call below
+        draws keyed noise instead of the device generator's — the keys are cut to the n samples produced, 'samples' uses
+        draw 0 (fork(0)), the in- and outpainting draws 1 and 2, the progressive row draw 3.  `seed` keeps its meaning
+        (one x_T shared by the batch, from the torch generator); the keys then give the step noise only.  The posterior
+        sample of the encoded batch (z: the reconstruction, the inpainting's x0) is keyed as well (rng.STREAM_POSTERIOR,
+        draw 0), so with keys log_images reads the torch generator nowhere but in plot_diffusion_rows, which stays on it."""
         use_ddim = ddim_steps is not None
         z, cond, x, xrec, _ = self.get_input(batch, self.first_stage_key, return_first_stage_outputs=True,
-                                             force_c_encode=True, return_original_cond=True, bs=N)
+                                             force_c_encode=True, return_original_cond=True, bs=N,
+                                             **({} if noise_keys is None else {"noise_keys": noise_keys}))
         n = min(x.shape[0], N)
         n_row = min(x.shape[0], n_row)
+        keyed = (lambda j: {}) if noise_keys is None else (lambda j: {"noise_keys": noise_keys[:n].fork(j)})
         log = {} if xrec is None else {"reconstruction": xrec}
         require(z is not None or not (plot_diffusion_rows or inpaint),
                 "diffusion rows and inpainting need the first stage's encoder", NotImplementedError)
@@ -598,7 +615,7 @@ class LatentDiffusion(AncestralSampling, DDPM):
                 x_T = torch.randn((1, self.channels, *self.image_size), device=self.device).repeat(n, 1, 1, 1)
             with self.ema_scope("Plotting"):
                 samples, z_denoise_row = self.sample_log(cond=cond, batch_size=n, ddim=use_ddim, ddim_steps=ddim_steps,
-                                                         eta=ddim_eta, x_T=x_T, **kwargs)
+                                                         eta=ddim_eta, x_T=x_T, **keyed(0), **kwargs)
             log["samples"] = self.decode_first_stage(samples)
             if plot_denoise_rows:
                 log["denoise_row"] = self._get_denoise_row_from_list(z_denoise_row)
@@ -612,19 +629,19 @@ class LatentDiffusion(AncestralSampling, DDPM):
                 mask = mask[:, None, ...]
                 with self.ema_scope("Plotting Inpaint"):
                     samples, _ = self.sample_log(cond=cond, batch_size=n, ddim=use_ddim, eta=ddim_eta,
-                                                 ddim_steps=ddim_steps, x0=z[:n], mask=mask)
+                                                 ddim_steps=ddim_steps, x0=z[:n], mask=mask, **keyed(1))
                 log["samples_inpainting"] = self.decode_first_stage(samples.to(self.device))
                 log["mask"] = mask
                 # "outpainting" runs with the SAME mask as the inpainting, as the reference does: a second draw of
                 # the same task (its own x_T), not the complementary one
                 with self.ema_scope("Plotting Outpaint"):
                     samples, _ = self.sample_log(cond=cond, batch_size=n, ddim=use_ddim, eta=ddim_eta,
-                                                 ddim_steps=ddim_steps, x0=z[:n], mask=mask)
+                                                 ddim_steps=ddim_steps, x0=z[:n], mask=mask, **keyed(2))
                 log["samples_outpainting"] = self.decode_first_stage(samples.to(self.device))
         if plot_progressive_rows:
             with self.ema_scope("Plotting Progressives"):
                 _, progressives = self.progressive_denoising(cond, shape=(self.channels, *self.image_size),
-                                                             batch_size=n)
+                                                             batch_size=n, **keyed(3))
             log["progressive_row"] = self._get_denoise_row_from_list(progressives, desc="Progressive Generation")
         if return_keys and any(k in log for k in return_keys):
             return {k: log[k] for k in return_keys}

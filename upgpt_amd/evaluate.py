@@ -173,15 +173,49 @@ def test_step(model, batch, batch_idx, **log_kwargs):
 test_step.__test__ = False  # (not a pytest test, whatever imports it)
 
 
-def run_test(model, batches, save_dir, **log_kwargs):
+def _keyed_batches(model, batches, noise_seed):
+    """(index, batch, NoiseKeys or None) per batch; sample ids are the running sample indices over the batches."""
+    from .rng import NoiseKeys
+    seen = 0
+    for j, batch in enumerate(batches):
+        keys = None
+        if noise_seed is not None:  # (without a seed the batch is not looked at: any batch object passes through)
+            n = int(batch[model.first_stage_key].shape[0])
+            keys = NoiseKeys(noise_seed, range(seen, seen + n), device=model.device)
+            keys.keys  # (uploaded here, with the batch: under host_io() when lanes take their batches)
+            seen += n
+        yield j, batch, keys
+
+
+def run_test(model, batches, save_dir, lanes=1, noise_seed=None, **log_kwargs):
     """What trainer.test(model, data) does with test_step (main.py:798), without Lightning: model.logger =
-    ResultDir(save_dir) for the duration, then test_step(batch, i, **log_kwargs) per batch.  Serial: the batches are
-    not spread over execution lanes (log_images draws from the process-wide device generator)."""
+    ResultDir(save_dir) for the duration (set once, also with lanes), then test_step(batch, i, **log_kwargs) per batch.
+    noise_seed (an int below 2^64): every batch samples with keyed noise, log_images(noise_keys=NoiseKeys(noise_seed,
+    ids)) — `ids` are the RUNNING sample indices over `batches` (first sample of the first batch = 0), so a sample's
+    noise, and with it its picture up to the GEMM tilings of its batch size, depends on neither batch_size nor the batch
+    it falls into; for run_split they are the dataset's indices.  The torch generator is not used for sampling.
+    lanes > 1: the batches are spread over that many execution lanes of a LanePool (upgpt_amd/lanes.py) and `noise_seed`
+    is required — without it log_images draws from the process-wide device generator and the lanes would interleave
+    those draws in an undefined order (ValueError).  Each lane thread takes the next batch from `batches` when it is free
+    (the iterator is advanced under _lib.host_io(): the loader's uploads and launches run on the taking lane's stream and
+    never overlap another lane's graph capture) and runs test_step in its lane — sampling, finishing, the one device ->
+    host copy and PIL's JPEG encoding all happen in the lane thread, outside the lock.  Files and bytes equal the
+    lanes=1 run with the same noise_seed (tests/test_lanes_eval_gpu.py).  An exception in a lane ends the run — the
+    other lanes finish the batch they are on and take no further one — and is re-raised; nothing is retried."""
+    lanes = int(lanes)
+    require(lanes >= 1, "lanes must be >= 1", ValueError)
+    require(lanes == 1 or noise_seed is not None, "lanes > 1 needs noise_seed: without keyed noise log_images draws from the "
+            "process-wide device generator, and lane threads would interleave those draws in an undefined order", ValueError)
     had, prev = "logger" in vars(model), vars(model).get("logger")
     model.logger = ResultDir(save_dir)
     try:
-        for i, batch in enumerate(batches):
-            model.test_step(batch, i, **log_kwargs)
+        work = _keyed_batches(model, batches, noise_seed)
+        kw = lambda keys: log_kwargs if keys is None else dict(log_kwargs, noise_keys=keys)
+        if lanes == 1:
+            for j, batch, keys in work:
+                model.test_step(batch, j, **kw(keys))
+        else:
+            _run_lanes(model, work, lanes, kw)
     finally:
         if had:
             model.logger = prev
@@ -190,15 +224,42 @@ def run_test(model, batches, save_dir, **log_kwargs):
     return Path(save_dir) / "results"
 
 
-def run_split(model, dataset, save_dir, batch_size=8, **log_kwargs):
+def _run_lanes(model, work, lanes, kw):
+    import threading
+
+    from .lanes import LanePool
+    take, failed = threading.Lock(), threading.Event()
+
+    def lane_loop(i):
+        while not failed.is_set():
+            try:
+                with take, _lib.host_io():  # (batch assembly: uploads and loader launches, on this lane's stream)
+                    item = next(work, None)
+                if item is None:
+                    return
+                j, batch, keys = item
+                model.test_step(batch, j, **kw(keys))
+            except BaseException:
+                failed.set()
+                raise
+
+    # one EMA scope around the run: the weight override does not go out and in again between the lanes' batches
+    with LanePool(lanes, device=model.device) as pool, model.ema_scope():
+        pool.run(lane_loop, lanes)  # "step" i = the whole loop of lane i, on lane i's thread and stream
+
+
+def run_split(model, dataset, save_dir, batch_size=8, lanes=1, noise_seed=None, **log_kwargs):
     """run_test over a dataset of this package (upgpt_amd/data.py: DeepFashionPair, the `target` of the model configs'
     test set): dataset.batches(batch_size) assembles every batch on the device, test_step writes its seven folders.
-    "dataset folder -> results/" with nothing supplied but paths and weights; run_metrics is the step after it."""
-    return run_test(model, dataset.batches(int(batch_size)), save_dir, **log_kwargs)
+    "dataset folder -> results/" with nothing supplied but paths and weights; run_metrics is the step after it.
+    lanes / noise_seed: as run_test; dataset.batches yields the samples in index order from 0 and does not expose the
+    indices, so the running sample index run_test keys the noise with IS the dataset index."""
+    return run_test(model, dataset.batches(int(batch_size)), save_dir, lanes=lanes, noise_seed=noise_seed, **log_kwargs)
 
 
 def run_validation(model, dataset, batch_size=8, seed=0, max_batches=None, save_dir=None):
-    """The validation epoch of trainer.validate without Lightning: dataset.batches(batch_size) (upgpt_amd/data.py; any
+    """(Serial, on the torch generator: lanes / noise_seed of run_test are not offered here.)
+    The validation epoch of trainer.validate without Lightning: dataset.batches(batch_size) (upgpt_amd/data.py; any
     object with that method, or a plain iterable of batch dicts) through model.validation_step, and the epoch means of
     its keys as Lightning's on_epoch reduction forms them — every batch's value weighted by the batch's size — as a plain
     {key: float} dict, e.g. 'val/loss_simple_ema', the number the UPGPT configs monitor.  With save_dir they are also
@@ -246,6 +307,7 @@ def run_upscale(model, batches, lr_dir, save_dir, pad=(8, 0), **log_kwargs):
     conditioning bytes share one device buffer that crosses to the host in one copy behind one synchronise, as in
     finished_arrays.  Written: save_dir/results/upscaled/<fname>.jpg and, the conditioning actually used,
     save_dir/results/lr/<fname>.jpg.  Returns the results directory.  The caller's batch dicts are left as they came.
+    Serial, on the torch generator: the lanes / noise_seed arguments of run_test are not offered here.
 
     This is THIS PACKAGE'S extension: the reference's own test_step cannot run on that dataset's batches, because it
     reads `smpl_image` and `src_image`, which the dataset does not provide.  N is the batch size here, unlike

@@ -12,6 +12,7 @@ import contextlib
 import numpy as np
 import torch
 
+from . import rng
 from .ddim import DDIMSampler
 from ._check import require
 from ._lib import host_io
@@ -31,6 +32,11 @@ class PLMSSampler(DDIMSampler):
                img_callback=None, quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0.,
                score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
                unconditional_guidance_scale=1., unconditional_conditioning=None, **kwargs):
+        """`noise_keys=` (through **kwargs; upgpt_amd.rng.NoiseKeys): x_T, when not given, is the keyed draw (STREAM_XT,
+        row 0) — the only normals PLMS uses (eta = 0).  The fast path then leaves the torch generator alone: the S + 1
+        draws the reference makes and discards are not made."""
+        noise_keys = kwargs.get("noise_keys")
+        rng.check_keys(noise_keys, batch_size, normals_sequence)
         acp = self.model.alphas_cumprod  # (tables of an unchanged (S, eta) are kept between calls, as in DDIMSampler.sample)
         key = (int(S), float(eta), id(self.model), acp.data_ptr(), int(getattr(acp, "_version", 0)), str(acp.device))
         if verbose or getattr(self, "_sched_key", None) != key:
@@ -45,13 +51,14 @@ class PLMSSampler(DDIMSampler):
                                   temperature=temperature, score_corrector=score_corrector,
                                   corrector_kwargs=corrector_kwargs, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning)
+                                  unconditional_conditioning=unconditional_conditioning, noise_keys=noise_keys)
 
     @torch.no_grad()
     def plms_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100,
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
-                      unconditional_guidance_scale=1., unconditional_conditioning=None):
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, noise_keys=None):
+        rng.check_keys(noise_keys, shape[0])
         if ddim_use_original_steps or quantize_denoised:
             raise NotImplementedError("PLMS with the original 1000 steps / quantized x0 is not on the UPGPT path")
         device = self.model.betas.device
@@ -65,8 +72,11 @@ class PLMSSampler(DDIMSampler):
                          unconditional_guidance_scale, unconditional_conditioning) \
                 and len(timesteps) == len(self.ddim_timesteps) and temperature == 1.:
             return self._fast_plms(cond, shape, x_T, timesteps, callback, img_callback, log_every_t,
-                                   unconditional_guidance_scale, unconditional_conditioning)
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device)
+                                   unconditional_guidance_scale, unconditional_conditioning, noise_keys)
+        if x_T is not None:
+            img = x_T.to(device)
+        else:
+            img = torch.randn(shape, device=device) if noise_keys is None else rng.randn(noise_keys, shape, rng.STREAM_XT)
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         time_range = np.flip(timesteps)
         total = timesteps.shape[0]
@@ -96,7 +106,8 @@ class PLMSSampler(DDIMSampler):
                 intermediates["pred_x0"].append(pred_x0)
         return img, intermediates
 
-    def _fast_plms(self, cond, shape, x_T, timesteps, callback, img_callback, log_every_t, cfg_scale, uc):
+    def _fast_plms(self, cond, shape, x_T, timesteps, callback, img_callback, log_every_t, cfg_scale, uc,
+                   noise_keys=None):
         from .ddim import ddim_coefficient_table
         from .engine import SamplerState
         model = self.model
@@ -128,7 +139,10 @@ class PLMSSampler(DDIMSampler):
             fresh = fresh_rows or fresh_coefs
             on_host = any(t is not None and torch.is_tensor(t) and not t.is_cuda for t in (x_T, c_concat, c_cross))
             with (host_io() if (fresh or on_host) else contextlib.nullcontext()):  # (ddim.py _fast_sampling: same rule)
-                img = torch.randn(shape, device=dev) if x_T is None else x_T.to(dev, torch.float32)
+                if x_T is not None:
+                    img = x_T.to(dev, torch.float32)
+                else:
+                    img = torch.randn(shape, device=dev) if noise_keys is None else rng.randn(noise_keys, shape, rng.STREAM_XT)
                 st.x.copy_(img)
                 plan.load_x_nchw(torch.cat([st.x, st.x]) if cfg else st.x, 0, 0)
                 if c_concat is not None:
@@ -142,7 +156,7 @@ class PLMSSampler(DDIMSampler):
                     st.coefs[:S].copy_(ddim_coefficient_table(self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sigmas,
                                                               self.ddim_sqrt_one_minus_alphas, order))
                     st._coef_key = ckey
-                for _ in range(S + 1):  # the reference draws (and, eta being 0, discards) one noise tensor per update:
+                for _ in range(S + 1 if noise_keys is None else 0):  # the reference draws (and, eta being 0, discards) one noise tensor per update:
                     torch.randn(shape, device=dev)  # plms.py get_x_prev_and_pred_x0 — same generator state afterwards
                 plan.step.zero_()
                 plan.prep.run()
