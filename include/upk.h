@@ -1065,6 +1065,39 @@ int upk_randn_keyed_f32(upk_ctx* ctx, const uint32_t* keys, int batch, long long
  * Errors as above. */
 int upk_philox_u32(upk_ctx* ctx, const uint32_t* keys, int batch, long long n, int row0, int rows, uint32_t stream_id,
                    uint32_t draw, uint32_t* out, upk_stream stream);
+/* The values of the counter's stream_id word the library itself uses (upgpt_amd/rng.py names 0 .. 3: x_T, the step noise,
+ * the q_sample noise of a sampler, the first stage's posterior sample). */
+#define UPK_STREAM_TIMESTEP 4   /* the timestep of a loss evaluation */
+#define UPK_STREAM_LOSS_NOISE 5 /* its noise */
+/* upk_q_sample_keyed_f32: upk_q_sample_f32 with the timestep and the noise drawn inside the kernel from the sample's key:
+ * one launch for upk_randn_keyed_f32 (a noise table) + a host-made t + upk_q_sample_f32.  Never allocates, never
+ * synchronises, graph-capturable, class "other".
+ *   keys             uint32 [batch, 2] on the device; draw: the counter's draw word (both as in upk_randn_keyed_f32)
+ *   x_start          fp32 NCHW [batch, c, hw], dense; a, s: the two fp32 schedule tables of n_t entries, as in upk_q_sample_f32
+ *   t_in             int32 [batch], or NULL.  NULL: t_b = (w0 * n_t) >> 32 as a 64-bit product, w0 = word 0 of the Philox call
+ *                    with counter (0, 0, UPK_STREAM_TIMESTEP, draw) and the key of sample b: uniform on [0, n_t), every value's
+ *                    probability within n_t * 2^-32 relative of 1 / n_t.  Non-NULL: t_b = t_in[b] (t_in == t_out is allowed)
+ *   t_out            int32 [batch], never NULL: t_b, what upk_p_losses_f32 and the forward plan's timestep rows read
+ *   noise            element e of sample b is n = the normal of counter (e >> 2, 0, UPK_STREAM_LOSS_NOISE, draw), word pair
+ *                    and transform as above: bit for bit what upk_randn_keyed_f32(rows = 1, row0 = 0, stream_id =
+ *                    UPK_STREAM_LOSS_NOISE, draw, row_scale = NULL) writes
+ *   noise_out        fp32 [batch, c, hw] <- n (the target of an eps model), or NULL
+ *   x_noisy          fp32 [batch, c, hw] <- v, or NULL
+ *   xin              fp16 NHWC [batch * hw, ld_xin] <- v rounded once to fp16 in channels [0, c), or NULL; channels >= c of a
+ *                    row are left untouched
+ * At least one of noise_out, x_noisy, xin must be given.  v = fl(fl(a[t_b] * x0) + fl(s[t_b] * n)), no FMA contraction: bit for
+ * bit what upk_q_sample_f32 gives for that noise and t.  A t_in[b] outside [0, n_t) is never used as an index: x_noisy and
+ * xin of that sample are NaN, its noise_out and the other samples are as without it.  A value depends on (key, draw, element)
+ * and x_start alone: not on batch, on the sample's position, on the alignment of a pointer or on the launch geometry.  A
+ * thread moves the four elements 4 q .. 4 q + 3 of a sample with one 16-byte load / store per tensor whose address of that
+ * quad is 16-byte aligned, element by element otherwise (and for the sample's last c * hw % 4 elements).
+ * Errors: UPK_EINVAL for null keys, x_start, tables or t_out, noise_out, x_noisy and xin all NULL, non-positive sizes,
+ * ld_xin < c, an fp32 / int32 / uint32 pointer not 4-byte or xin not 2-byte aligned; UPK_ESHAPE for c * hw above
+ * 2^31 - 1 - 8192. */
+int upk_q_sample_keyed_f32(upk_ctx* ctx, const uint32_t* keys, uint32_t draw, const float* x_start, const int32_t* t_in,
+                           const float* sqrt_alphas_cumprod, const float* sqrt_one_minus_alphas_cumprod, int n_t,
+                           int32_t* t_out, float* noise_out, float* x_noisy, void* xin, int ld_xin, int batch, int c, int hw,
+                           upk_stream stream);
 
 /* ------------------------------------------------------------------ */
 /* HIP graph helpers (the 50-step loop replays one captured step).      */

@@ -33,7 +33,7 @@ SYMBOLS = [
     "upk_lpips_input_f16", "upk_relu_pool_nhwc_f16", "upk_lpips_ws_bytes", "upk_lpips_layer_f16",
     "upk_conv2d_rect_f16", "upk_pool3_nhwc_f16", "upk_fid_input_f16", "upk_avgpool_global_f32",
     "upk_q_sample_f32", "upk_p_losses_ws_bytes", "upk_p_losses_f32",
-    "upk_randn_keyed_f32", "upk_philox_u32",
+    "upk_randn_keyed_f32", "upk_philox_u32", "upk_q_sample_keyed_f32",
     "upk_advance_step", "upk_step_autoadvance", "upk_kernel_launches", "upk_graph_begin", "upk_graph_end", "upk_graph_launch", "upk_graph_destroy",
     "upk_prof_enable", "upk_prof_collect",
     "upk_stream_create_cumask", "upk_stream_destroy", "upk_probe_placement", "upk_probe_clock",
@@ -226,6 +226,7 @@ def load_library(path=None):
                                            C.c_size_t, vp]),
             "upk_randn_keyed_f32": (C.c_int, [vp, vp, i32, i64, i32, i32, C.c_uint32, C.c_uint32, vp, vp, vp]),
             "upk_philox_u32": (C.c_int, [vp, vp, i32, i64, i32, i32, C.c_uint32, C.c_uint32, vp, vp]),
+            "upk_q_sample_keyed_f32": (C.c_int, [vp, vp, C.c_uint32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
             "upk_advance_step": (C.c_int, [vp, vp, vp]),
             "upk_step_autoadvance": (C.c_int, [vp, vp]),
             "upk_kernel_launches": (C.c_longlong, [vp, i32]),
@@ -535,6 +536,14 @@ class Context:
         """upk_philox_u32: out [rows, batch, n] <- the raw Philox word of every element (32-bit storage)."""
         self._chk(self.lib.upk_philox_u32(self.h, _ptr(keys), int(batch), int(n), int(row0), int(rows), int(stream_id),
                                           int(draw), _ptr(out), self._s()))
+
+    def q_sample_keyed(self, keys, draw, x_start, t_in, sqrt_ac, sqrt_1m_ac, n_t, t_out, noise_out, x_noisy, xin, ld_xin,
+                       batch, c, hw):
+        """upk_q_sample_keyed_f32: upk_q_sample_f32 with the timestep (t_in None) and the noise drawn inside the kernel from
+        the samples' keys; t_out int32 [batch] <- the timesteps used, noise_out / x_noisy / xin each optional."""
+        self._chk(self.lib.upk_q_sample_keyed_f32(self.h, _ptr(keys), int(draw), _ptr(x_start), _ptr(t_in), _ptr(sqrt_ac),
+                                                  _ptr(sqrt_1m_ac), int(n_t), _ptr(t_out), _ptr(noise_out), _ptr(x_noisy),
+                                                  _ptr(xin), int(ld_xin), int(batch), int(c), int(hw), self._s()))
 
     def step_autoadvance(self, done):
         """Arms (done: zeroed device int32) or disarms (None) the step kernels' own increment of *step."""

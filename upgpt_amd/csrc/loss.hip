@@ -6,6 +6,15 @@
 // q_sample_kernel   one thread per 4 consecutive elements of the flat [B * C * HW] tensors (16-byte loads and stores) plus
 //                   one thread per element of the n % 4 tail; without 16-byte aligned pointers every element is a tail
 //                   element.  A group may cross a channel or a sample: (sample, channel, pixel) walk along with it.
+// q_sample_keyed_kernel  upk_q_sample_keyed_f32: a workgroup takes KTILE = 1024 consecutive elements of ONE sample per turn
+//                   and walks the (sample, tile) pairs grid-stride; thread t owns quad e / 4 = tile * 256 + t of the sample,
+//                   makes its Philox call and the two Box-Muller pairs (philox.h: the device functions of rng.hip) and
+//                   noises its four elements.  Nothing of the launch, the batch or the addresses enters a value.  The
+//                   sample is uniform over the workgroup, so its key, its timestep (the Philox call of STREAM_TIMESTEP, or
+//                   t_in) and the two table entries are wave-uniform loads.  A quad moves with one 16-byte load / store
+//                   per tensor where that tensor's address of the quad is 16-byte aligned (a sample starts at base + b * c
+//                   * hw: aligned only by luck when c * hw % 4 != 0 or the base is offset) and element by element
+//                   otherwise, as does the sample's tail of c * hw % 4 elements.  No LDS, no barrier.
 // p_losses_partial  one workgroup (256 threads) per (sample, chunk of 4096 elements of its C * HW): the fp32 terms e and
 //                   w * e are widened to fp64 as they are made and summed per thread, per wave (shuffles), then over the
 //                   four waves in a fixed order into the workgroup's OWN slot of ws (no atomics).  The element -> (thread,
@@ -15,6 +24,7 @@
 //                   shuffle tree: an order that depends on C * HW alone), forms the sample's terms in fp64 and adds them
 //                   to the wave's batch sums; thread 0 adds the four waves' sums in order and writes the batch scalars.
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -81,6 +91,94 @@ __global__ __launch_bounds__(NT) void q_sample_kernel(const QArgs p) {
       *(f32x4*)(p.xn + i) = o;
     } else {
       p.xn[i] = v[0];
+    }
+  }
+}
+
+struct KArgs {
+  const uint32_t* keys;  // [batch, 2]
+  const float* x0;
+  const int32_t* t_in;   // or nullptr: the keyed timestep
+  const float* ta;
+  const float* ts;
+  int32_t* t_out;
+  float* nz;
+  float* xn;
+  f16* xin;
+  long total_tiles;
+  int tiles_per_seg, n_t, c, hw, chw, ld;
+  uint32_t draw;
+};
+
+constexpr int KTILE = NT * 4;
+
+__global__ __launch_bounds__(NT) void q_sample_keyed_kernel(const KArgs p) {
+  const int tid = threadIdx.x;
+  for (long w = blockIdx.x; w < p.total_tiles; w += gridDim.x) {
+    const long b = w / p.tiles_per_seg;
+    const int tile = (int)(w - b * p.tiles_per_seg);
+    const uint32_t k0 = p.keys[2 * b], k1 = p.keys[2 * b + 1];
+    int tb;
+    if (p.t_in) {
+      tb = p.t_in[b];
+    } else {
+      uint32_t tw[4];
+      philox4x32_10(0u, 0u, (uint32_t)UPK_STREAM_TIMESTEP, p.draw, k0, k1, tw);
+      tb = (int)(((uint64_t)tw[0] * (uint64_t)(uint32_t)p.n_t) >> 32);
+    }
+    if (tile == 0 && tid == 0) p.t_out[b] = tb;
+    const bool ok = (unsigned)tb < (unsigned)p.n_t;  // (a timestep outside the tables is never used as an index)
+    const float a = ok ? p.ta[tb] : __builtin_nanf(""), s = ok ? p.ts[tb] : __builtin_nanf("");
+    const int e = tile * KTILE + 4 * tid;
+    if (e >= p.chw) continue;
+    const int cnt = min(4, p.chw - e);
+    uint32_t q[4];
+    philox4x32_10((uint32_t)(e >> 2), 0u, (uint32_t)UPK_STREAM_LOSS_NOISE, p.draw, k0, k1, q);
+    float z[4], x0[4], v[4];
+    box_muller(q[0], q[1], z[0], z[1]);
+    box_muller(q[2], q[3], z[2], z[3]);
+    const long i = b * p.chw + e;
+    const float* px0 = p.x0 + i;
+    if (cnt == 4 && !((uintptr_t)px0 & 15)) {
+      const f32x4 m = *(const f32x4*)px0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) x0[j] = m[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) x0[j] = j < cnt ? px0[j] : 0.0f;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float lhs = a * x0[j], rhs = s * z[j];
+      v[j] = lhs + rhs;
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      float* dst = k == 0 ? p.nz : p.xn;
+      const float* src = k == 0 ? z : v;
+      if (!dst) continue;
+      dst += i;
+      if (cnt == 4 && !((uintptr_t)dst & 15)) {
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = src[j];
+        *(f32x4*)dst = o;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (j < cnt) dst[j] = src[j];
+      }
+    }
+    if (p.xin) {
+      int c = e / p.hw, px = e - c * p.hw;
+      f16* row = p.xin + b * p.hw * p.ld;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (j < cnt) {
+          row[(long)px * p.ld + c] = (f16)v[j];
+          if (++px == p.hw) px = 0, ++c;
+        }
+      }
     }
   }
 }
@@ -228,6 +326,34 @@ extern "C" int upk_q_sample_f32(upk_ctx* ctx, const float* x_start, const float*
   upk_prof_scope prof(ctx, UPK_CLS_OTHER, stream);
   hipLaunchKernelGGL(q_sample_kernel, dim3((unsigned)blocks), dim3(NT), 0, stream, qa);
   return upk_check_launch(ctx, "q_sample");
+}
+
+extern "C" int upk_q_sample_keyed_f32(upk_ctx* ctx, const uint32_t* keys, uint32_t draw, const float* x_start,
+                                      const int32_t* t_in, const float* sqrt_alphas_cumprod,
+                                      const float* sqrt_one_minus_alphas_cumprod, int n_t, int32_t* t_out, float* noise_out,
+                                      float* x_noisy, void* xin, int ld_xin, int batch, int c, int hw, upk_stream stream_) {
+  if (!ctx) return UPK_EINVAL;
+  if (!keys || !x_start || !sqrt_alphas_cumprod || !sqrt_one_minus_alphas_cumprod || !t_out)
+    return upk_fail(ctx, UPK_EINVAL, "q_sample_keyed: null pointer");
+  if (!noise_out && !x_noisy && !xin) return upk_fail(ctx, UPK_EINVAL, "q_sample_keyed: noise_out, x_noisy and xin are all null");
+  if (batch <= 0 || c <= 0 || hw <= 0 || n_t <= 0) return upk_fail(ctx, UPK_EINVAL, "q_sample_keyed: sizes must be positive");
+  if (xin && ld_xin < c) return upk_fail(ctx, UPK_EINVAL, "q_sample_keyed: ld_xin = %d below c = %d", ld_xin, c);
+  if (((uintptr_t)keys | (uintptr_t)x_start | (uintptr_t)t_in | (uintptr_t)sqrt_alphas_cumprod |
+       (uintptr_t)sqrt_one_minus_alphas_cumprod | (uintptr_t)t_out | (uintptr_t)noise_out | (uintptr_t)x_noisy) & 3)
+    return upk_fail(ctx, UPK_EINVAL, "q_sample_keyed: an fp32 / int32 pointer is not 4-byte aligned");
+  if ((uintptr_t)xin & 1) return upk_fail(ctx, UPK_EINVAL, "q_sample_keyed: xin is not 2-byte aligned");
+  if (!blocks_per_sample(c, hw)) return upk_fail(ctx, UPK_ESHAPE, "q_sample_keyed: c * hw = %ld too large", (long)c * hw);
+  KArgs ka;
+  ka.keys = keys, ka.x0 = x_start, ka.t_in = t_in, ka.ta = sqrt_alphas_cumprod, ka.ts = sqrt_one_minus_alphas_cumprod;
+  ka.t_out = t_out, ka.nz = noise_out, ka.xn = x_noisy, ka.xin = (f16*)xin;
+  ka.n_t = n_t, ka.c = c, ka.hw = hw, ka.chw = c * hw, ka.ld = ld_xin, ka.draw = draw;
+  ka.tiles_per_seg = (ka.chw + KTILE - 1) / KTILE;
+  ka.total_tiles = (long)batch * ka.tiles_per_seg;
+  const unsigned grid = (unsigned)(ka.total_tiles < 65536L ? ka.total_tiles : 65536L);  // (the tiles beyond go grid-stride)
+  hipStream_t stream = (hipStream_t)stream_;
+  upk_prof_scope prof(ctx, UPK_CLS_OTHER, stream);
+  hipLaunchKernelGGL(q_sample_keyed_kernel, dim3(grid), dim3(NT), 0, stream, ka);
+  return upk_check_launch(ctx, "q_sample_keyed");
 }
 
 extern "C" size_t upk_p_losses_ws_bytes(int batch, int c, int hw) {

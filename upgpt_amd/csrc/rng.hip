@@ -1,7 +1,7 @@
 // Keyed (counter-based) device noise: upk_randn_keyed_f32 fills a [rows, batch, n] table of scaled standard normals,
 // upk_philox_u32 the raw Philox words of the same elements.  Generator, counter layout, transform and error codes are
 // stated in include/upk.h.  This file is compiled with -ffp-contract=off: the transform below is one fp32 operation
-// at a time around logf / sqrtf / sincospif.
+// at a time around logf / sqrtf / sincospif (philox.h: the generator and the transform, shared with loss.hip).
 //
 // fill_kernel<NORMAL>  a workgroup (256 threads) takes TILE = 1024 consecutive elements of one (row, sample) segment per
 //                      turn and walks the tiles of the whole table grid-stride, so a value is a function of (key, element,
@@ -14,6 +14,7 @@
 //                      VALU (10 Philox rounds, two log / sqrt / sincospi per quad) and stores only; no global load but the
 //                      wave-uniform key and scale.
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -30,30 +31,6 @@ struct RArgs {
   int batch, row0;
   uint32_t stream, draw;
 };
-
-// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants)
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t (&w)[4]) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0;
-    const uint32_t hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
-    c0 = hi1 ^ c1 ^ k0, c1 = lo1, c2 = hi0 ^ c3 ^ k1, c3 = lo0;
-    k0 += W0, k1 += W1;
-  }
-  w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
-}
-
-// (w_a, w_b) -> (z_a, z_b): include/upk.h.  u1, u2 and 2 u2 are exact in fp32; the angle 2 pi u2 is never rounded
-__device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, float& za, float& zb) {
-  const float u1 = (float)((wa >> 8) + 1u) * 0x1p-24f;
-  const float u2 = (float)(wb >> 8) * 0x1p-24f;
-  const float r = sqrtf(-2.0f * logf(u1));
-  float s, c;
-  sincospif(2.0f * u2, &s, &c);
-  za = r * c, zb = r * s;
-}
 
 template <bool NORMAL>
 __global__ __launch_bounds__(NT) void fill_kernel(const RArgs p) {

@@ -456,17 +456,20 @@ class DeepFashionPair:
     def _finish(self, batch):
         return {k: batch[k] for k in self.batch_keys()}
 
-    def batches(self, batch_size, start=0, stop=None):
+    def batches(self, batch_size, start=0, stop=None, batch_start=0, batch_step=1):
         """Yields the batch dicts of samples [start, stop) in order, batch_size per dict (the last one may be smaller):
         tensors on the current device, `txt` and `fname` lists of strings.  Keys and key order are the reference's:
         image, txt, fname, src_image, styles, smpl, smpl_image, person_mask, and loss_w when loss_weight is set (image and
         txt only with image_only=True).  image / src_image / smpl_image fp32 [B, H, W, 3]; styles [B, 9, 3, 224, 224];
         smpl [B, 1, n] in the pickles' dtype; person_mask / loss_w [B, 1, h, w].  Per batch: one upload, the launches, and
-        in 'bbox' mode one device -> host copy of the [B, 4] boxes (an all-zero mask is refused)."""
-        batch_size = int(batch_size)
+        in 'bbox' mode one device -> host copy of the [B, 4] boxes (an all-zero mask is refused).
+        batch_start, batch_step: only the batches batch_start, batch_start + batch_step, ... of that sequence are built
+        (a shard of an evaluation, evaluate.run_validation(rank=, world=)); the others are never decoded."""
+        batch_size, batch_start, batch_step = int(batch_size), int(batch_start), int(batch_step)
         require(batch_size >= 1, "batch_size must be positive", ValueError)
+        require(batch_start >= 0 and batch_step >= 1, "batch_start must be >= 0 and batch_step >= 1", ValueError)
         idx = list(range(len(self)))[start:stop]
-        for i in range(0, len(idx), batch_size):
+        for i in range(batch_start * batch_size, len(idx), batch_size * batch_step):
             yield self._finish(self._assemble(self._samples(idx[i:i + batch_size])))
 
     def __getitem__(self, index):
@@ -492,9 +495,10 @@ class DeepFashionSample(DeepFashionPair):
     def _samples(self, names):
         return [(n, n, None) for n in names]
 
-    def batches(self, batch_size, start=0, stop=None, names=None):
-        batch_size = int(batch_size)
+    def batches(self, batch_size, start=0, stop=None, names=None, batch_start=0, batch_step=1):
+        batch_size, batch_start, batch_step = int(batch_size), int(batch_start), int(batch_step)
         require(batch_size >= 1, "batch_size must be positive", ValueError)
+        require(batch_start >= 0 and batch_step >= 1, "batch_start must be >= 0 and batch_step >= 1", ValueError)
         names = list(self.map if names is None else names)[start:stop]
-        for i in range(0, len(names), batch_size):
+        for i in range(batch_start * batch_size, len(names), batch_size * batch_step):
             yield self._finish(self._assemble(self._samples(names[i:i + batch_size])))

@@ -37,6 +37,7 @@ from ._check import require
 
 
 _EMA_LOCK = threading.Lock()
+_LAST_KEYED = threading.local()  # .terms: (t, loss_terms) of the calling thread's last keyed p_losses (lanes share the model)
 
 
 def disabled_train(self, mode=True):
@@ -177,21 +178,32 @@ class DDPM(nn.Module):
         require(not torch.isnan(self.lvlb_weights).all(), "lvlb_weights are all NaN", AssertionError)
 
     @contextmanager
-    def ema_scope(self, context=None):
+    def ema_scope(self, context=None, local=False):
         """ddpm.py:179-192.  Inside the scope the denoiser COMPUTES with the LitEma shadow
         weights; they are packed straight from the shadow buffers instead of being copied
-        over the live parameters (same results, no 1.7 GB copy + repack per call)."""
+        over the live parameters (same results, no 1.7 GB copy + repack per call).
+        local=True (an extension): the selection holds for the CALLING THREAD alone and takes precedence over the
+        process-wide one (UNetModel.set_weight_local) — a lane thread in the EMA pass of its validation batch leaves the
+        other lanes on the weight set they are on.  No lock and no count: the previous selection of the thread is put back."""
         if not self.use_ema:
             yield None
             return
+        unet, ema = self.model.diffusion_model, self.model_ema
+        sel = ("ema", lambda n: ema.shadow("diffusion_model." + n).data,
+               lambda: (sum(b._version for b in ema.buffers()), ema.decay.data_ptr()))
+        if local:
+            prev = unet.set_weight_local(sel)
+            try:
+                yield None
+            finally:
+                unet.set_weight_local(prev)
+            return
         # the scope nests and may be entered from several host threads at once (one per execution lane): the override
         # goes in with the first entrant and out with the last
-        unet, ema = self.model.diffusion_model, self.model_ema
         with _EMA_LOCK:
             n = self.__dict__.get("_ema_depth", 0)
             if n == 0:
-                unet.set_weight_override("ema", lambda n: ema.shadow("diffusion_model." + n).data,
-                                         lambda: (sum(b._version for b in ema.buffers()), ema.decay.data_ptr()))
+                unet.set_weight_override(*sel)
             self.__dict__["_ema_depth"] = n + 1
         if context is not None:
             print(f"{context}: Switched to EMA weights")
@@ -466,7 +478,7 @@ class LatentDiffusion(AncestralSampling, DDPM):
 
     # ---- the validation loss
     @torch.no_grad()
-    def p_losses(self, x_start, cond, t, noise=None, loss_w=None):
+    def p_losses(self, x_start, cond, t, noise=None, loss_w=None, noise_keys=None):
         """ddpm.py:1083-1123 -> (loss, loss_dict), forward only.  loss_dict has the reference's keys under its prefix
         ('train' if self.training else 'val'): <prefix>/loss_simple, <prefix>/loss_vlb, <prefix>/loss, and with
         learn_logvar also <prefix>/loss_gamma and 'logvar'; the values are 0-dim fp32 device tensors.
@@ -477,11 +489,21 @@ class LatentDiffusion(AncestralSampling, DDPM):
         per sample, and upk_p_losses_f32 reduces its fp32 output against the target (fixed-order fp64 sums, no
         atomics): three launches around the forward and no host synchronisation.  self.loss_terms keeps the kernel's
         whole output of the last call: {loss, loss_simple, loss_gamma, loss_vlb}, then {simple, plain} per sample.
+        noise_keys (upgpt_amd.rng.NoiseKeys, one key per sample, in batch order; an extension): the noise is the keyed
+        draw rng.STREAM_LOSS_NOISE made INSIDE upk_q_sample_keyed_f32, which takes the place of randn_like and
+        upk_q_sample_f32 — no noise table, no generator.  t may then be None: the timesteps are the keyed draw
+        rng.STREAM_TIMESTEP of the same launch; a given t is honoured.  self.loss_t keeps the int32 [B] timesteps of the
+        last keyed call.  Keys together with noise= (both name the noise) or in another number than B: ValueError.
         NOT reproduced: the reference's `image = self.decode_first_stage(model_output)` (its line 1089) decodes the
         model output to a picture and drops it; nothing is decoded here."""
+        from . import rng
+        require(x_start.dim() == 4, "p_losses: x_start [B, C, H, W] and t [B]", ValueError)
+        rng.check_keys(noise_keys, x_start.shape[0])  # (the argument checks come before any device work)
+        require(noise_keys is None or noise is None, "noise_keys and noise both name the noise: give one", ValueError)
         unet = self.model.diffusion_model
         dev = unet._device()  # (RuntimeError on a CPU model: there is no CPU fallback)
-        require(x_start.dim() == 4 and t.shape[0] == x_start.shape[0], "p_losses: x_start [B, C, H, W] and t [B]", ValueError)
+        require(t is not None or noise_keys is not None, "p_losses: t may be None only with noise_keys", ValueError)
+        require(t is None or t.shape[0] == x_start.shape[0], "p_losses: x_start [B, C, H, W] and t [B]", ValueError)
         require(self.loss_type in ("l1", "l2"), "unknown loss type '%s'" % (self.loss_type,), NotImplementedError)
         B, C, H, W = x_start.shape
         cc, ca = self._split_cond(cond)
@@ -492,15 +514,25 @@ class LatentDiffusion(AncestralSampling, DDPM):
         ctx, n_t = pl.ctx, self.num_timesteps
         with torch.cuda.device(dev):
             x_start = x_start.to(dev, torch.float32).contiguous()
-            noise = torch.randn_like(x_start) if noise is None else noise.to(dev, torch.float32).contiguous()
-            require(noise.shape == x_start.shape, "p_losses: noise and x_start differ in shape", ValueError)
-            t32 = t.to(dev, torch.int32).contiguous()
             wc = 0
             if loss_w is not None:
                 wc = 1 if loss_w.dim() == 4 and loss_w.shape[1] == 1 else C
                 loss_w = loss_w.to(dev, torch.float32).expand(B, wc, H, W).contiguous()
-            ctx.q_sample(x_start, noise, t32, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, n_t, None,
-                         pl.xin.t, pl.xin.ld, B, C, H * W)
+            if noise_keys is None:
+                noise = torch.randn_like(x_start) if noise is None else noise.to(dev, torch.float32).contiguous()
+                require(noise.shape == x_start.shape, "p_losses: noise and x_start differ in shape", ValueError)
+                t32 = t.to(dev, torch.int32).contiguous()
+                ctx.q_sample(x_start, noise, t32, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, n_t, None,
+                             pl.xin.t, pl.xin.ld, B, C, H * W)
+            else:
+                eps = self.parameterization == "eps"
+                noise = torch.empty_like(x_start) if eps else None  # (an x0 model has no use for the noise itself)
+                t32 = torch.empty(B, dtype=torch.int32, device=dev)
+                t_in = None if t is None else t.to(dev, torch.int32).contiguous()
+                ctx.q_sample_keyed(noise_keys.keys, noise_keys.draw, x_start, t_in, self.sqrt_alphas_cumprod,
+                                   self.sqrt_one_minus_alphas_cumprod, n_t, t32, noise, None, pl.xin.t, pl.xin.ld, B, C, H * W)
+                self.__dict__["loss_t"] = t32
+                _LAST_KEYED.terms = None
             if cc is not None:
                 pl.load_x_nchw(cc, C, pl.cin_pad)
             pl.t_rows.copy_(t32)
@@ -525,39 +557,84 @@ class LatentDiffusion(AncestralSampling, DDPM):
             loss_dict[prefix + "/loss_vlb"] = out[3]
             loss_dict[prefix + "/loss"] = out[0]
             self.__dict__["loss_terms"] = out  # (the kernel's whole output of the last call, for diagnostics)
+            if noise_keys is not None:
+                _LAST_KEYED.terms = (t32, out)
         return out[0], loss_dict
 
-    def forward(self, x, c, *args, **kwargs):
-        """ddpm.py:941-950: one uniformly drawn timestep per sample (on the device), then p_losses."""
-        t = torch.randint(0, self.num_timesteps, (x.shape[0],), device=self.device).long()
+    def forward(self, x, c, *args, noise_keys=None, **kwargs):
+        """ddpm.py:941-950: one uniformly drawn timestep per sample (on the device), then p_losses.  With noise_keys the
+        timesteps are the keyed draw of p_losses' own launch and the torch generator is not read."""
         if self.model.conditioning_key is not None:
             require(c is not None, "a conditional model needs its conditioning", AssertionError)
+        if noise_keys is not None:
+            return self.p_losses(x, c, None, *args, noise_keys=noise_keys, **kwargs)
+        t = torch.randint(0, self.num_timesteps, (x.shape[0],), device=self.device).long()
         return self.p_losses(x, c, t, *args, **kwargs)
 
-    def shared_step(self, batch, **kwargs):
-        """ddpm.py:931-939."""
-        x, c, w = self.get_input(batch, self.first_stage_key, return_loss_w=True)
-        return self(x, c, loss_w=w)
+    def shared_step(self, batch, noise_keys=None, **kwargs):
+        """ddpm.py:931-939.  noise_keys: the posterior sample, the timesteps and the noise are keyed draws."""
+        if noise_keys is None:
+            x, c, w = self.get_input(batch, self.first_stage_key, return_loss_w=True)
+            return self(x, c, loss_w=w)
+        x, c, w = self.get_input(batch, self.first_stage_key, return_loss_w=True, noise_keys=noise_keys)
+        return self(x, c, loss_w=w, noise_keys=noise_keys)
+
+    PER_SAMPLE = "per_sample"  # validation_step(noise_keys=): the key of the per-sample table in the returned dict
 
     @torch.no_grad()
-    def validation_step(self, batch, batch_idx=0):
+    def validation_step(self, batch, batch_idx=0, noise_keys=None):
         """ddpm.py:364-371: the loss_dict of the live weights and, under the suffix '_ema', of the EMA weights (inside
         ema_scope()).  The reference hands both to Lightning's log_dict (on_epoch means); here the merged dict is
         RETURNED (evaluate.run_validation forms the epoch means) and also passed to self.log_dict when the instance
         has one.  The encoder moments and the conditioning are computed once and shared by the two passes; each pass
-        draws its own posterior sample, timesteps and noise, in the reference's order (live first)."""
+        draws its own posterior sample, timesteps and noise, in the reference's order (live first).
+        noise_keys (upgpt_amd.rng.NoiseKeys, one key per sample, in batch order): the three draws of a pass are keyed —
+        the posterior sample (rng.STREAM_POSTERIOR), the timesteps and the noise (upk_q_sample_keyed_f32) — with
+        noise_keys.fork(0) for the live pass and fork(1) for the EMA pass, so a sample meets the same draws whatever
+        batch it falls into, and the torch generator is not read.  The EMA pass selects the shadow weights for the
+        calling thread alone (ema_scope(local=True)): lanes may sit on different weight sets.  The returned dict then
+        ALSO holds, under the key 'per_sample' (LatentDiffusion.PER_SAMPLE), a device fp64 tensor [B, 6] with the columns
+        t, simple, plain, t_ema, simple_ema, plain_ema of every sample; that entry is NOT a loss, is not handed to
+        log_dict and is left out of the epoch reduction (evaluate.run_validation forms the epoch means FROM it)."""
+        from . import rng
+        rng.check_keys(noise_keys, batch[self.first_stage_key].shape[0])
         dev = self.model.diffusion_model._device()
         x = DDPM.get_input(self, batch, self.first_stage_key).to(dev)
         posterior = self.encode_first_stage(x)
         _, c, w = self.get_input(batch, self.first_stage_key, return_loss_w=True, encode_image=False)
-        _, merged = self(self.get_first_stage_encoding(posterior).detach(), c, loss_w=w)
-        with self.ema_scope():
-            _, ema = self(self.get_first_stage_encoding(posterior).detach(), c, loss_w=w)
+        if noise_keys is None:
+            _, merged = self(self.get_first_stage_encoding(posterior).detach(), c, loss_w=w)
+            with self.ema_scope():
+                _, ema = self(self.get_first_stage_encoding(posterior).detach(), c, loss_w=w)
+            rows = None
+        else:
+            unet = self.model.diffusion_model
+            B = x.shape[0]
+            rows = torch.empty(B, 6, dtype=torch.float64, device=dev)
+
+            def one_pass(j):
+                keys = noise_keys.fork(j)
+                nz = rng.randn(keys, tuple(posterior.mean.shape), rng.STREAM_POSTERIOR)
+                _, d = self(self.get_first_stage_encoding(posterior, noise=nz).detach(), c, loss_w=w, noise_keys=keys)
+                t32, terms = _LAST_KEYED.terms  # (this thread's: self.loss_terms may be another lane's by now)
+                rows[:, 3 * j] = t32
+                rows[:, 3 * j + 1:3 * j + 3] = terms[4:].view(B, 2)
+                return d
+
+            prev = unet.set_weight_local("live")  # (the live pass is live whatever scope the caller sits in)
+            try:
+                merged = one_pass(0)
+            finally:
+                unet.set_weight_local(prev)
+            with self.ema_scope(local=True):
+                ema = one_pass(1)
         merged = dict(merged)
         merged.update({k + "_ema": v for k, v in ema.items()})
         log_dict = getattr(self, "log_dict", None)
         if callable(log_dict):
             log_dict(merged, prog_bar=False, logger=True, on_step=False, on_epoch=True)
+        if rows is not None:
+            merged[self.PER_SAMPLE] = rows
         return merged
 
     # ---- sampling / logging (continued)

@@ -12,6 +12,10 @@ metrics.txt with per-image SSIM and MS-SSIM from upk_ssim_u8 (upgpt_amd/metrics.
 public weight files, LPIPS (upgpt_amd/lpips.py) and, given pytorch_fid's Inception weights, the FID line of
 metrics.txt (upgpt_amd/fid.py); `python -m upgpt_amd.evaluate --dir <save_dir>/results` runs it.
 
+run_validation is the validation epoch (val/loss_simple_ema, the number a checkpoint is picked by); with noise_seed= every
+sample meets the same keyed draws whatever its batch, lane or rank shard, and merge_validation forms the epoch means of
+shards.
+
 run_upscale is the second model's pass over a results tree: results/samples-sized pictures -> the `lr` conditioning on the
 device (upgpt_amd/prepare.py, upk_resize_bilinear_u8) -> the upscale model -> results/upscaled.
 """
@@ -215,7 +219,7 @@ def run_test(model, batches, save_dir, lanes=1, noise_seed=None, **log_kwargs):
             for j, batch, keys in work:
                 model.test_step(batch, j, **kw(keys))
         else:
-            _run_lanes(model, work, lanes, kw)
+            _run_lanes(model, work, lanes, lambda item: model.test_step(item[1], item[0], **kw(item[2])))
     finally:
         if had:
             model.logger = prev
@@ -224,7 +228,13 @@ def run_test(model, batches, save_dir, lanes=1, noise_seed=None, **log_kwargs):
     return Path(save_dir) / "results"
 
 
-def _run_lanes(model, work, lanes, kw):
+def _run_lanes(model, work, lanes, step, ema=True):
+    """The lane loop of run_test / run_validation / run_upscale: every lane thread takes the next item of the iterator
+    `work` when it is free — under the take lock and _lib.host_io(), so whatever the iterator does to produce an item
+    (decoding, uploads, loader launches) runs on the taking lane's stream, one taker at a time — and calls step(item) in
+    its lane, outside the lock.  ema: one process-wide EMA scope around the run (the flows that only sample); a flow that
+    alternates the weight sets per batch passes False and selects per thread (ema_scope(local=True))."""
+    import contextlib
     import threading
 
     from .lanes import LanePool
@@ -237,14 +247,13 @@ def _run_lanes(model, work, lanes, kw):
                     item = next(work, None)
                 if item is None:
                     return
-                j, batch, keys = item
-                model.test_step(batch, j, **kw(keys))
+                step(item)
             except BaseException:
                 failed.set()
                 raise
 
     # one EMA scope around the run: the weight override does not go out and in again between the lanes' batches
-    with LanePool(lanes, device=model.device) as pool, model.ema_scope():
+    with LanePool(lanes, device=model.device) as pool, (model.ema_scope() if ema else contextlib.nullcontext()):
         pool.run(lane_loop, lanes)  # "step" i = the whole loop of lane i, on lane i's thread and stream
 
 
@@ -257,19 +266,191 @@ def run_split(model, dataset, save_dir, batch_size=8, lanes=1, noise_seed=None, 
     return run_test(model, dataset.batches(int(batch_size)), save_dir, lanes=lanes, noise_seed=noise_seed, **log_kwargs)
 
 
-def run_validation(model, dataset, batch_size=8, seed=0, max_batches=None, save_dir=None):
-    """(Serial, on the torch generator: lanes / noise_seed of run_test are not offered here.)
-    The validation epoch of trainer.validate without Lightning: dataset.batches(batch_size) (upgpt_amd/data.py; any
+VAL_COLUMNS = ("id", "t", "simple", "plain", "t_ema", "simple_ema", "plain_ema")
+
+
+def shard_batches(n_batches, rank, world):
+    """The batch indices a call with (rank, world) processes: j in [0, n_batches) with j % world == rank."""
+    rank, world = int(rank), int(world)
+    require(world >= 1 and 0 <= rank < world, "rank must be in [0, world), got rank %d of %d" % (rank, world), ValueError)
+    return list(range(rank, int(n_batches), world))
+
+
+def _shard_work(dataset, batch_size, rank, world, max_batches):
+    """(global batch index j, id of its first sample, batch) for the batches of this shard, in order.  A dataset whose
+    batches() takes batch_start / batch_step (upgpt_amd/data.py) is asked for its own batches only — the others are never
+    decoded — and the first id is j * batch_size (every batch but the last is full); any other source is walked through
+    and counted."""
+    import inspect
+    fn = getattr(dataset, "batches", None) if batch_size is not None else None  # (None: `dataset` IS the batches)
+    limit = None if max_batches is None else int(max_batches)
+    if fn is not None and "batch_step" in inspect.signature(fn).parameters:
+        for k, batch in enumerate(fn(batch_size, batch_start=rank, batch_step=world)):
+            j = rank + k * world
+            if limit is not None and j >= limit:
+                return
+            yield j, j * batch_size, batch
+        return
+    seen = 0
+    for j, batch in enumerate(fn(batch_size) if fn is not None else dataset):
+        if limit is not None and j >= limit:
+            return
+        first, seen = seen, seen + _batch_len(batch)
+        if j % world == rank:
+            yield j, first, batch
+
+
+def _batch_len(batch):
+    for v in batch.values():
+        if torch.is_tensor(v) or isinstance(v, (list, tuple)):
+            return len(v)
+    raise ValueError("a batch without a tensor or a list: its size is unknown")
+
+
+def _val_schedule(model, lvlb, logvar):
+    """What the epoch means need besides the per-sample table (val_schedule.json): the loss weights and the two tables
+    indexed by t (host sequences of the fp32 values widened to double)."""
+    return {"prefix": "train" if model.training else "val", "l_simple_weight": float(model.l_simple_weight),
+            "original_elbo_weight": float(model.original_elbo_weight), "learn_logvar": bool(model.learn_logvar),
+            "lvlb_weights": [float(v) for v in lvlb], "logvar": [float(v) for v in logvar]}
+
+
+def _ordered_sum(values):
+    s = 0.0
+    for v in values:  # (in sample-index order, one fp64 addition at a time: the order is part of the result)
+        s += float(v)
+    return s
+
+
+def validation_means(table, sched):
+    """The epoch means of a keyed validation run from its per-sample table: fp64 [N, 6] in sample-index order, columns
+    t, simple, plain, t_ema, simple_ema, plain_ema (upk_p_losses_f32's per-sample values).  Formed as upk_p_losses_f32
+    forms a batch's values, over the whole epoch and in fp64: loss_simple = mean simple, loss_gamma = mean(simple /
+    exp(logvar[t]) + logvar[t]), loss_vlb = mean(lvlb_weights[t] * plain), loss = l_simple_weight * loss_gamma +
+    original_elbo_weight * loss_vlb — Lightning's on_epoch mean of the batch means, weighted by the batch sizes, is the
+    mean over the samples.  Keys and their order are validation_step's."""
+    import math
+    table = np.asarray(table, dtype=np.float64)
+    require(table.ndim == 2 and table.shape[1] == 6 and table.shape[0] > 0, "validation_means: an [N, 6] table", ValueError)
+    n, p = table.shape[0], sched["prefix"]
+    lvlb, logvar = sched["lvlb_weights"], sched["logvar"]
+    out = {}
+    for suffix, off in (("", 0), ("_ema", 3)):
+        t = [int(v) for v in table[:, off]]
+        require(all(0 <= v < len(lvlb) for v in t), "validation_means: a timestep outside the schedule", ValueError)
+        simple, plain = table[:, off + 1], table[:, off + 2]
+        m_simple = _ordered_sum(simple) / n
+        m_gamma = _ordered_sum(float(s) / math.exp(logvar[k]) + logvar[k] for s, k in zip(simple, t)) / n
+        m_vlb = _ordered_sum(lvlb[k] * float(q) for q, k in zip(plain, t)) / n
+        out[p + "/loss_simple" + suffix] = m_simple
+        if sched["learn_logvar"]:
+            out[p + "/loss_gamma" + suffix] = m_gamma
+            out["logvar" + suffix] = _ordered_sum(logvar) / len(logvar)
+        out[p + "/loss_vlb" + suffix] = m_vlb
+        out[p + "/loss" + suffix] = sched["l_simple_weight"] * m_gamma + sched["original_elbo_weight"] * m_vlb
+    return out
+
+
+def _write_val_samples(path, ids, table):
+    with open(path, "w") as f:
+        f.write(",".join(VAL_COLUMNS) + "\n")
+        for i, row in zip(ids, table):  # (repr of a double reads back as the same double)
+            f.write("%d,%d,%r,%r,%d,%r,%r\n" % (i, int(row[0]), float(row[1]), float(row[2]), int(row[3]), float(row[4]),
+                                                 float(row[5])))
+
+
+def _read_val_samples(path):
+    with open(path) as f:
+        lines = [ln.strip() for ln in f if ln.strip()]
+    require(lines and tuple(lines[0].split(",")) == VAL_COLUMNS, "%s: the header is not %s" % (path, ",".join(VAL_COLUMNS)),
+            ValueError)
+    ids, rows = [], []
+    for ln in lines[1:]:
+        cells = ln.split(",")
+        require(len(cells) == len(VAL_COLUMNS), "%s: a row of %d cells" % (path, len(cells)), ValueError)
+        ids.append(int(cells[0]))
+        rows.append([float(c) for c in cells[1:]])
+    return ids, rows
+
+
+def merge_validation(save_dir):
+    """The epoch means of a validation run that was evaluated in shards: reads every <save_dir>/val_samples.rank<r>of<w>.csv
+    (run_validation(rank=r, world=w, save_dir=...)) and val_schedule.json, puts the rows into sample-index order and forms
+    the means with validation_means — bit for bit the values of the world = 1 run with the same batch_size and noise_seed.
+    Refused (ValueError): no shard, shards of different `world`, a rank missing or present twice, a sample id in two
+    rows, and a gap in the ids 0 .. N - 1.  Writes val_metrics.json and the merged val_samples.csv; returns the means.
+    No collective and no torch.distributed call: the shards meet in the directory."""
+    import json
+    import re
+    save_dir = Path(save_dir)
+    found = {}
+    for name in sorted(os.listdir(str(save_dir))):
+        m = re.fullmatch(r"val_samples\.rank(\d+)of(\d+)\.csv", name)
+        if m:
+            found[name] = (int(m.group(1)), int(m.group(2)))
+    require(found, "merge_validation: no val_samples.rank<r>of<w>.csv in %s" % save_dir, ValueError)
+    worlds = sorted({w for _, w in found.values()})
+    require(len(worlds) == 1, "merge_validation: shards of different world sizes %s" % worlds, ValueError)
+    ranks = sorted(r for r, _ in found.values())
+    require(ranks == list(range(worlds[0])), "merge_validation: ranks %s of %d: every rank once" % (ranks, worlds[0]), ValueError)
+    ids, rows = [], []
+    for name in found:
+        i, r = _read_val_samples(save_dir / name)
+        ids += i
+        rows += r
+    require(len(set(ids)) == len(ids), lambda: "merge_validation: sample ids in more than one row: %s" % sorted(
+        {i for i in ids if ids.count(i) > 1})[:8], ValueError)
+    order = sorted(range(len(ids)), key=ids.__getitem__)
+    ids = [ids[k] for k in order]
+    require(ids == list(range(len(ids))), lambda: "merge_validation: the sample ids have gaps: %s missing" % sorted(
+        set(range(max(ids) + 1)) - set(ids))[:8], ValueError)
+    table = np.array([rows[k] for k in order], dtype=np.float64)
+    with open(save_dir / "val_schedule.json") as f:
+        sched = json.load(f)
+    means = validation_means(table, sched)
+    _write_val_samples(save_dir / "val_samples.csv", ids, table)
+    with open(save_dir / "val_metrics.json", "w") as f:
+        json.dump(means, f, indent=1)
+    return means
+
+
+def run_validation(model, dataset, batch_size=8, seed=0, max_batches=None, save_dir=None, lanes=1, noise_seed=None, rank=0,
+                   world=1):
+    """The validation epoch of trainer.validate without Lightning: dataset.batches(batch_size) (upgpt_amd/data.py; any
     object with that method, or a plain iterable of batch dicts) through model.validation_step, and the epoch means of
     its keys as Lightning's on_epoch reduction forms them — every batch's value weighted by the batch's size — as a plain
     {key: float} dict, e.g. 'val/loss_simple_ema', the number the UPGPT configs monitor.  With save_dir they are also
     written to <save_dir>/val_metrics.json.
-    The timesteps, the noise and the posterior samples come from the device generator, seeded with `seed` for the
-    duration (the generators' states are put back afterwards), so a run is repeatable.  The values stay on the device:
-    they are accumulated there in fp64 and cross to the host in one copy behind the run's only synchronise."""
+    Without noise_seed the timesteps, the noise and the posterior samples come from the device generator, seeded with
+    `seed` for the duration (the generators' states are put back afterwards), so a run is repeatable.  The values stay
+    on the device: they are accumulated there in fp64 and cross to the host in one copy behind the run's only synchronise.
+    noise_seed (an int below 2^64): validation_step(noise_keys=NoiseKeys(noise_seed, ids)) — `ids` are the RUNNING sample
+    indices over the batches, as in run_test — so sample i meets the same (t, noise, posterior noise) whatever
+    batch_size, max_batches or checkpoint, and two checkpoints differ by a paired difference; `seed` is not used.  The
+    per-sample values {t, simple, plain} of both passes are gathered in a device fp64 table in batch-index order, cross
+    to the host in one copy behind the run's one synchronise, and the epoch means are formed FROM that table in
+    sample-index order (validation_means), so they do not depend on which lane finished first: lanes = 1, 2 and 4 give
+    the same bits under the same tuning table (_lib.shared_chip).
+    lanes > 1: the batches are spread over execution lanes as in run_test (noise_seed required: ValueError); the live and
+    the EMA pass of a batch select their weight set for the lane's thread alone, so lanes sit on different sets.
+    rank, world: this call evaluates the batches j with j % world == rank (noise_seed required); a dataset of
+    upgpt_amd.data is asked for those batches only.  The ids stay the global running indices.  The returned means are
+    the SHARD's; merge_validation(save_dir) forms the epoch's from the shards' files.
+    save_dir with noise_seed: val_samples.csv (world > 1: val_samples.rank<r>of<w>.csv) with the columns id, t, simple,
+    plain, t_ema, simple_ema, plain_ema; val_schedule.json (the loss weights and tables validation_means reads); and,
+    with world = 1, val_metrics.json."""
     import json
+    lanes, rank, world, batch_size = int(lanes), int(rank), int(world), int(batch_size)
+    require(lanes >= 1, "lanes must be >= 1", ValueError)
+    require(lanes == 1 or noise_seed is not None, "lanes > 1 needs noise_seed: without keyed noise validation_step draws from "
+            "the process-wide device generator, and lane threads would interleave those draws in an undefined order", ValueError)
+    require(world >= 1 and 0 <= rank < world, "rank must be in [0, world), got rank %d of %d" % (rank, world), ValueError)
+    require(world == 1 or noise_seed is not None, "world > 1 needs noise_seed: without keyed noise a sample's draws depend on "
+            "the batches evaluated before it", ValueError)
     dev = model.model.diffusion_model._device()
-    batches = dataset.batches(int(batch_size)) if hasattr(dataset, "batches") else dataset
+    if noise_seed is not None:
+        return _run_validation_keyed(model, dataset, batch_size, max_batches, save_dir, lanes, int(noise_seed), rank, world, dev)
+    batches = dataset.batches(batch_size) if hasattr(dataset, "batches") else dataset
     keys, acc, count = None, None, 0
     with torch.cuda.device(dev), torch.random.fork_rng(devices=[dev.index]):
         torch.manual_seed(int(seed))
@@ -296,7 +477,58 @@ def run_validation(model, dataset, batch_size=8, seed=0, max_batches=None, save_
     return means
 
 
-def run_upscale(model, batches, lr_dir, save_dir, pad=(8, 0), **log_kwargs):
+def _run_validation_keyed(model, dataset, batch_size, max_batches, save_dir, lanes, noise_seed, rank, world, dev):
+    import json
+
+    from .rng import NoiseKeys
+    per_sample = type(model).PER_SAMPLE
+    done = {}  # global batch index -> (id of its first sample, device fp64 [n, 6])
+
+    def work():
+        for j, first, batch in _shard_work(dataset, batch_size, rank, world, max_batches):
+            n = int(batch[model.first_stage_key].shape[0])
+            keys = NoiseKeys(noise_seed, range(first, first + n), device=dev)
+            keys.keys  # (uploaded here, with the batch: under host_io() when lanes take their batches)
+            yield j, first, batch, keys
+
+    def step(item):
+        j, first, batch, keys = item
+        done[j] = (first, model.validation_step(batch, j, noise_keys=keys)[per_sample])
+
+    with torch.cuda.device(dev):
+        model._logvar_table(dev)  # (a host logvar is uploaded here, once, not from a lane thread beside a capture)
+        if lanes == 1:
+            for item in work():
+                step(item)
+        else:
+            _run_lanes(model, work(), lanes, step, ema=False)
+        require(done, "run_validation: no batches", ValueError)
+        order = sorted(done)
+        # batch-index order, whichever lane made which batch; the two tables of the loss ride along in the one copy
+        n_t = int(model.num_timesteps)
+        blob = torch.cat([done[j][1].reshape(-1) for j in order] + [model.lvlb_weights.to(dev).double(),
+                                                                    model._logvar_table(dev).double()])
+        host = torch.empty(blob.numel(), dtype=torch.float64, pin_memory=True)
+        host.copy_(blob, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+    arr = host.numpy().copy()
+    table, lvlb, logvar = arr[:-2 * n_t].reshape(-1, 6), arr[-2 * n_t:-n_t], arr[-n_t:]
+    ids = [i for j in order for i in range(done[j][0], done[j][0] + int(done[j][1].shape[0]))]
+    sched = _val_schedule(model, lvlb, logvar)
+    means = validation_means(table, sched)
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+        name = "val_samples.csv" if world == 1 else "val_samples.rank%dof%d.csv" % (rank, world)
+        _write_val_samples(os.path.join(str(save_dir), name), ids, table)
+        with open(os.path.join(str(save_dir), "val_schedule.json"), "w") as f:
+            json.dump(sched, f)
+        if world == 1:
+            with open(os.path.join(str(save_dir), "val_metrics.json"), "w") as f:
+                json.dump(means, f, indent=1)
+    return means
+
+
+def run_upscale(model, batches, lr_dir, save_dir, pad=(8, 0), lanes=1, noise_seed=None, rank=0, world=1, **log_kwargs):
     """The second stage of an evaluation run, the flow of the reference's DeepFashionSuperResSampling dataset
     (deepfashion_inshop.py:419-479) through the upscale model: for every batch dict (`fname`, `styles`, `txt`, `image`)
     the low-resolution pictures lr_dir/<fname>.jpg are decoded by PIL, uploaded as bytes and turned into batch['lr']
@@ -307,7 +539,13 @@ def run_upscale(model, batches, lr_dir, save_dir, pad=(8, 0), **log_kwargs):
     conditioning bytes share one device buffer that crosses to the host in one copy behind one synchronise, as in
     finished_arrays.  Written: save_dir/results/upscaled/<fname>.jpg and, the conditioning actually used,
     save_dir/results/lr/<fname>.jpg.  Returns the results directory.  The caller's batch dicts are left as they came.
-    Serial, on the torch generator: the lanes / noise_seed arguments of run_test are not offered here.
+    noise_seed / lanes / rank, world: as run_test and run_validation.  With noise_seed every batch samples with
+    log_images(noise_keys=NoiseKeys(noise_seed, ids)), `ids` the running sample indices over `batches`; lanes > 1 (needs
+    noise_seed: ValueError) spreads the batches over execution lanes — PIL's decoding of the lr pictures and their upload
+    happen under the take lock (one taker at a time, on the taking lane's stream), the chain, the finishing, the one
+    device -> host copy and the JPEG encoding in the lane thread — and writes the files of the lanes = 1 run with the same
+    seed byte for byte under the same tuning table (_lib.shared_chip); rank, world (needs noise_seed) processes the
+    batches j with j % world == rank, the ids staying the global ones.
 
     This is THIS PACKAGE'S extension: the reference's own test_step cannot run on that dataset's batches, because it
     reads `smpl_image` and `src_image`, which the dataset does not provide.  N is the batch size here, unlike
@@ -316,6 +554,13 @@ def run_upscale(model, batches, lr_dir, save_dir, pad=(8, 0), **log_kwargs):
     from PIL import Image
 
     from . import prepare
+    lanes, rank, world = int(lanes), int(rank), int(world)
+    require(lanes >= 1, "lanes must be >= 1", ValueError)
+    require(lanes == 1 or noise_seed is not None, "lanes > 1 needs noise_seed: without keyed noise log_images draws from the "
+            "process-wide device generator, and lane threads would interleave those draws in an undefined order", ValueError)
+    require(world >= 1 and 0 <= rank < world, "rank must be in [0, world), got rank %d of %d" % (rank, world), ValueError)
+    require(world == 1 or noise_seed is not None, "world > 1 needs noise_seed: without keyed noise a sample's draws depend on "
+            "the batches evaluated before it", ValueError)
     lr_dir = Path(lr_dir)
     roots = {k: Path(save_dir) / "results" / k for k in ("upscaled", "lr")}
     for r in roots.values():
@@ -325,25 +570,40 @@ def run_upscale(model, batches, lr_dir, save_dir, pad=(8, 0), **log_kwargs):
     f = 2 ** int(model.num_downs)
     win = center_crop_window(f * oh, f * ow, model.crop_size)
     ch, cw = win[2], win[3]
-    for batch in batches:
-        names = list(batch["fname"])
+
+    def work():  # (what a lane does under the take lock: decoding, the upload, the keys)
+        from .rng import NoiseKeys
+        for j, first, batch in _shard_work(batches, None, rank, world, None):
+            names = list(batch["fname"])
+            pics = []
+            for fname in names:
+                path = lr_dir / f"{fname}.jpg"
+                arr = _decode(path) if path.is_file() else None
+                require(arr is not None, "run_upscale: cannot read the low-resolution picture %s" % path, ValueError)
+                require(not pics or arr.shape == pics[0].shape, "run_upscale: %s is %s, the first picture of its batch %s" % (
+                    path, arr.shape, pics[0].shape if pics else None), ValueError)
+                pics.append(arr)
+            src = torch.from_numpy(np.stack(pics)).to(dev, non_blocking=True)
+            if lanes > 1:  # (the conditioning crosses here, under the lock, not from the lane thread beside a capture)
+                batch = {k: v.to(dev) if torch.is_tensor(v) else v for k, v in batch.items()}
+            keys = None
+            if noise_seed is not None:
+                keys = NoiseKeys(noise_seed, range(first, first + len(names)), device=dev)
+                keys.keys
+            yield batch, names, src, keys
+
+    def step(item):
+        batch, names, src, keys = item
         n = len(names)
-        pics = []
-        for fname in names:
-            path = lr_dir / f"{fname}.jpg"
-            arr = _decode(path) if path.is_file() else None
-            require(arr is not None, "run_upscale: cannot read the low-resolution picture %s" % path, ValueError)
-            require(not pics or arr.shape == pics[0].shape, "run_upscale: %s is %s, the first picture of its batch %s" % (
-                path, arr.shape, pics[0].shape if pics else None), ValueError)
-            pics.append(arr)
         off_lr = (n * ch * cw * 3 + 15) // 16 * 16
         total = off_lr + n * oh * ow * 3
         buf = torch.empty(total, dtype=torch.uint8, device=dev)
         up_view = buf[:n * ch * cw * 3].view(n, ch, cw, 3)
         lr_view = buf[off_lr:].view(n, oh, ow, 3)
-        src = torch.from_numpy(np.stack(pics)).to(dev, non_blocking=True)
         kw = dict(LOG_DEFAULTS, N=n, use_ema=model.use_ema)
         kw.update(log_kwargs)
+        if keys is not None:
+            kw["noise_keys"] = keys
         with torch.no_grad():
             lr, lr_image = prepare.lr_transform(src, [oh, ow], pad, out_u8=lr_view)
             log = model.log_images(dict(batch, lr=lr, lr_image=lr_image), **kw)
@@ -363,6 +623,12 @@ def run_upscale(model, batches, lr_dir, save_dir, pad=(8, 0), **log_kwargs):
             if i < m:
                 Image.fromarray(up_arr[i]).save(roots["upscaled"] / f"{fname}.jpg")
             Image.fromarray(lr_arr[i]).save(roots["lr"] / f"{fname}.jpg")
+
+    if lanes == 1:
+        for item in work():
+            step(item)
+    else:
+        _run_lanes(model, work(), lanes, step)
     return Path(save_dir) / "results"
 
 

@@ -5,7 +5,8 @@ rank: NoiseKeys(seed, ids) gives every sample a 64-bit Philox key derived from (
 (include/upk.h: Philox4x32-10, counter (element >> 2, row, stream, draw), Box-Muller) fills a whole [rows, B, n] noise
 table in ONE launch on the caller's own stream — no torch generator, no generator state, no lock.  The samplers take
 the keys as `noise_keys=` (ddim.py, plms.py, ancestral.py), log_images forwards them, evaluate.run_test builds them from
-`noise_seed`.  DESIGN.md 28.
+`noise_seed`.  DESIGN.md 28.  The loss surface takes them too (p_losses / forward / shared_step / validation_step,
+evaluate.run_validation(noise_seed=)): there the timestep and the noise are drawn inside upk_q_sample_keyed_f32.  DESIGN.md 29.
 
 The key derivation runs on the host in numpy and is restated independently in tests/rng_ref.py.
 """
@@ -19,6 +20,8 @@ from ._lib import get_context
 # sample never share a Philox call
 STREAM_XT, STREAM_STEP, STREAM_QSAMPLE = 0, 1, 2
 STREAM_POSTERIOR = 3  # the first stage's posterior sample of an encoded batch (LatentDiffusion.get_input)
+# the two draws of a loss evaluation, made inside upk_q_sample_keyed_f32 (UPK_STREAM_TIMESTEP, UPK_STREAM_LOSS_NOISE)
+STREAM_TIMESTEP, STREAM_LOSS_NOISE = 4, 5
 
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 _MASK = np.uint64(0xFFFFFFFF)

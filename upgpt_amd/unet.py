@@ -4,12 +4,16 @@ hand-written HIP kernels of libupk.so.  Weights live in a ParamTree with the ref
 state-dict keys (time_embed.0.weight, input_blocks.1.1.transformer_blocks.0.attn2.to_k.weight,
 out.2.weight, ...)."""
 import os
+import threading
 
 import torch
 
 from .arch import UNetArch
 from .params import ParamTree, weights_fingerprint
 from ._check import require
+
+# thread -> {id(unet): selection}: a module-level object, so that a model still copies and pickles
+_WEIGHT_LOCAL = threading.local()
 
 
 class UNetModel(ParamTree):
@@ -48,6 +52,24 @@ class UNetModel(ParamTree):
         parameters; `fingerprint` is a callable used to invalidate the packed cache."""
         self._weight_override = None if tag is None else (tag, getter, fingerprint)
 
+    def set_weight_local(self, sel):
+        """The CALLING THREAD's weight set, ahead of the process-wide override: None (no selection of its own: the
+        process-wide one holds), "live" (the parameters, whatever the override says) or a (tag, getter, fingerprint)
+        triple as set_weight_override takes.  Returns the previous selection, to be put back.  A lane thread in its EMA
+        pass selects the shadow weights for itself alone: the packed sets and their plans are cached side by side under
+        their tag, so the other lanes go on with the set they are on."""
+        mine = _WEIGHT_LOCAL.__dict__.setdefault("sel", {})
+        prev = mine.pop(id(self), None)
+        if sel is not None:
+            mine[id(self)] = sel
+        return prev
+
+    def _weight_selection(self):
+        sel = getattr(_WEIGHT_LOCAL, "sel", {}).get(id(self))
+        if sel is None:
+            return self._weight_override
+        return None if sel == "live" else sel
+
     def packed(self):
         from ._lib import PLAN_LOCK
         with PLAN_LOCK:
@@ -58,12 +80,13 @@ class UNetModel(ParamTree):
         from .engine import PackedUNet
         dev = self._device()
         ctx = get_context(dev)
-        if self._weight_override is None:
+        sel = self._weight_selection()
+        if sel is None:
             tag, fp = "live", weights_fingerprint(self)
             params = dict(self.named_parameters())
             get = lambda n: params[n].data
         else:
-            tag, get, fpf = self._weight_override
+            tag, get, fpf = sel
             fp = fpf()
         ent = self._packed.get(tag)
         if ent is None or ent[0] != fp:
