@@ -555,8 +555,23 @@ int upk_ddpm_step_f32(upk_ctx* ctx, float* x, const float* model_out, const floa
 int upk_plms_step_f32(upk_ctx* ctx, float* x, const float* eps, const float* coefs, const int32_t* step,
                       float* hist, float* pred_x0, void* xin, int ld_xin, int batch, int c, int hw,
                       float cfg_scale, int cfg, upk_stream stream);
+/* One step of DPM-Solver++(2M) (Lu et al. 2022, algorithm 2: second-order multistep on the data prediction, eta = 0), fp32
+ * NCHW, n = B*C*H*W elements; row = coefs + 8 * (*step) for the step t -> p, lambda = log(alpha / sigma), h = lambda_p - lambda_t:
+ *   {sigma_t, 1/alpha_t, sigma_p/sigma_t, -alpha_p * expm1(-h), w, 0, 0, 0},  w = h / (2 h_prev) on a second-order row, 0 on a
+ *   first-order one (upgpt_amd/schedule.py dpm_coefficient_table)
+ *   e = eps, or with cfg != 0 e_u + cfg_scale * (e_c - e_u) from eps = [uncond ; cond] (2*batch rows)
+ *   p0 = (x - row[0]*e) * row[1];  second = row[4] != 0 && *step != first_row
+ *   D = second ? p0 + row[4] * (p0 - x0_old) : p0;  x = row[2]*x + row[3]*D;  x0_old = p0;  pred_x0 = p0 (may be NULL)
+ * x0_old: fp32 [n], the data prediction of the step before, owned by the caller.  It is READ ONLY when `second` holds — a
+ * first-order row (row 0, the chain's first row first_row, a lower-order final row) never touches what it held, so it needs
+ * no initialisation — and always written.  A first-order row is the DDIM eta = 0 update.  step == NULL: row 0.
+ * Refreshes the UNet stem input xin like upk_ddim_step_f32 (with cfg both halves, 2*batch*hw rows); x is updated in
+ * place; honours upk_step_autoadvance. */
+int upk_dpmpp_2m_step_f32(upk_ctx* ctx, float* x, const float* eps, const float* coefs, const int32_t* step,
+                          float* x0_old, float* pred_x0, void* xin, int ld_xin, int batch, int c, int hw,
+                          int first_row, float cfg_scale, int cfg, upk_stream stream);
 /* With done != NULL the sampler step kernels launched afterwards (upk_ddim_step_f32, upk_ddim_step_cfg_f32,
- * upk_ddim_step_edit_f32, upk_plms_step_f32, upk_ddpm_step_f32) add 1 to *step THEMSELVES once every workgroup has read it (done: a zero-initialised device
+ * upk_ddim_step_edit_f32, upk_plms_step_f32, upk_ddpm_step_f32, upk_dpmpp_2m_step_f32) add 1 to *step THEMSELVES once every workgroup has read it (done: a zero-initialised device
  * int32 they use as arrival counter and leave at zero) — one launch less per sampler step than upk_advance_step.
  * done == NULL restores the plain behaviour.  Host-side state of the context: set it around the calls. */
 int upk_step_autoadvance(upk_ctx* ctx, int32_t* done);

@@ -25,7 +25,7 @@ SYMBOLS = [
     "upk_attention_f16", "upk_groupnorm_nhwc_f16", "upk_groupnorm_stats_nhwc_f16", "upk_groupnorm_chunks", "upk_groupnorm_apply_nhwc_f16", "upk_groupnorm_finalize_f32", "upk_groupnorm_ws_bytes",
     "upk_layernorm_f16", "upk_timestep_embed_f16",
     "upk_nchw_f32_to_nhwc_f16", "upk_nhwc_f16_to_nchw_f32", "upk_f32_to_f16", "upk_ddim_step_f32",
-    "upk_ddim_step_cfg_f32", "upk_ddim_step_edit_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
+    "upk_ddim_step_cfg_f32", "upk_ddim_step_edit_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_dpmpp_2m_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
     "upk_attention_fewkeys_f16", "upk_gelu_f16",
     "upk_patchify_nchw_f32_f16", "upk_vit_assemble_f16", "upk_gather_rows_f16",
     "upk_image_finish_u8", "upk_resize_bilinear_u8", "upk_segm_boxes_u8", "upk_style_crops_u8",
@@ -196,6 +196,7 @@ def load_library(path=None):
             "upk_ddim_step_edit_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, f32,
                                                  i32, vp]),
             "upk_plms_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),
+            "upk_dpmpp_2m_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]),
             "upk_ddpm_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
             "upk_image_finish_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i64, i32, i32, i32, i32, vp, i64, i32, i64, i32,
                                               C.POINTER(C.c_float), vp]),
@@ -401,6 +402,13 @@ class Context:
         self._chk(self.lib.upk_plms_step_f32(self.h, _ptr(x), _ptr(eps), _ptr(coefs), _ptr(step), _ptr(hist),
                                              _ptr(pred_x0), _ptr(xin), ld_xin, batch, c, hw, float(cfg_scale), int(cfg),
                                              self._s()))
+
+    def dpmpp_2m_step(self, x, eps, coefs, step, x0_old, pred_x0, xin, ld_xin, batch, c, hw, first_row=0, cfg_scale=1.0,
+                      cfg=False):
+        """upk_dpmpp_2m_step_f32: x0_old is read only on a second-order row that is not `first_row`."""
+        self._chk(self.lib.upk_dpmpp_2m_step_f32(self.h, _ptr(x), _ptr(eps), _ptr(coefs), _ptr(step), _ptr(x0_old),
+                                                 _ptr(pred_x0), _ptr(xin), ld_xin, batch, c, hw, int(first_row),
+                                                 float(cfg_scale), int(cfg), self._s()))
 
     def image_finish(self, src, layout, batch, src_h, src_w, src_bs, top, left, crop_h, crop_w, dst, pitch, dst_x,
                      dst_bs, mode, denorm=None):

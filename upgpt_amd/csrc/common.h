@@ -178,3 +178,17 @@ __device__ __forceinline__ float upk_geglu_mul(float v, float g) {
   const float q = p * t * e;
   return v * fmaf(ag * q, -0.5f, fmaxf(g, 0.0f));
 }
+
+// The sampler step kernels advance the device-side step counter themselves (upk_step_autoadvance): every block has read
+// *step before it arrives at `done`; the block that arrives last bumps the counter and re-arms `done`.  One launch
+// less per step than a separate increment kernel; the next kernel sees the new value across the launch boundary.
+__device__ __forceinline__ void step_advance(const int* step, int* done) {
+  __syncthreads();
+  if (done && threadIdx.x == 0) {
+    __threadfence();
+    if (atomicAdd((unsigned*)done, 1u) == gridDim.x - 1) {
+      *done = 0;
+      *(int*)step = *step + 1;
+    }
+  }
+}

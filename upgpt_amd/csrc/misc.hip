@@ -178,20 +178,6 @@ __global__ void f32_to_f16_kernel(const float* x, int rows, int cols, f16* y, in
   y[r * ldy + cidx] = (f16)x[idx];
 }
 
-// The sampler step kernels advance the device-side step counter themselves (upk_step_autoadvance): every block has read
-// *step before it arrives at `done`; the block that arrives last bumps the counter and re-arms `done`.  One launch
-// less per step than a separate increment kernel; the next kernel sees the new value across the launch boundary.
-__device__ __forceinline__ void step_advance(const int* step, int* done) {
-  __syncthreads();
-  if (done && threadIdx.x == 0) {
-    __threadfence();
-    if (atomicAdd((unsigned*)done, 1u) == gridDim.x - 1) {
-      *done = 0;
-      *(int*)step = *step + 1;
-    }
-  }
-}
-
 // ddim.py:189-203 in one launch (see include/upk.h for the coefficient table).
 __global__ void ddim_step_kernel(float* x, const float* eps, const float* coefs, const float* noise, const int* step,
                                  float* pred_x0, f16* xin, int ld_xin, int c, int hw, long n, int* done) {

@@ -49,11 +49,14 @@ class DDIMSampler(object):
             attr = attr.to(self.model.device)
         setattr(self, name, attr)
 
+    def _make_timesteps(self, discretize, num_steps, verbose):
+        """The grid of make_schedule (a subclass may know more grids: dpm_solver.py)."""
+        return make_ddim_timesteps(ddim_discr_method=discretize, num_ddim_timesteps=num_steps,
+                                   num_ddpm_timesteps=self.ddpm_num_timesteps, verbose=verbose)
+
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0., verbose=True):
         self._sched_key = None  # (sample() keeps the tables of an unchanged (S, eta); a direct call always rebuilds)
-        self.ddim_timesteps = make_ddim_timesteps(ddim_discr_method=ddim_discretize,
-                                                  num_ddim_timesteps=ddim_num_steps,
-                                                  num_ddpm_timesteps=self.ddpm_num_timesteps, verbose=verbose)
+        self.ddim_timesteps = self._make_timesteps(ddim_discretize, ddim_num_steps, verbose)
         acp = self.model.alphas_cumprod
         require(acp.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep", ValueError)
         f32 = lambda x: torch.as_tensor(x).clone().detach().to(torch.float32).to(self.model.device)

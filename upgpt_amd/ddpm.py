@@ -639,11 +639,19 @@ class LatentDiffusion(AncestralSampling, DDPM):
 
     # ---- sampling / logging (continued)
     @torch.no_grad()
-    def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
-        """ddpm.py:1312-1325."""
+    def sample_log(self, cond, batch_size, ddim, ddim_steps, sampler="ddim", **kwargs):
+        """ddpm.py:1312-1325.  sampler (this package's extension; it arrives through log_images' **kwargs, so test_step,
+        evaluate.run_test / run_upscale and InferenceModel.generate take it too): "ddim", or "dpmpp_2m" for
+        DPM-Solver++(2M) on its logSNR grid (dpm_solver.py) — ddim_steps is then its step count, and `eta`, DDIM's knob
+        (log_images passes its ddim_eta default of 1), does not apply to the deterministic solver and is dropped."""
+        require(sampler in ("ddim", "dpmpp_2m"), lambda: "sampler %r (ddim or dpmpp_2m)" % (sampler,), ValueError)
         if not ddim:
             return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, **kwargs)
         shape = (self.channels, *self.image_size)
+        if sampler == "dpmpp_2m":
+            from .dpm_solver import DPMSolverSampler
+            kwargs.pop("eta", None)
+            return DPMSolverSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
         return DDIMSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
 
     def _get_denoise_row_from_list(self, samples, desc="", force_no_decoder_quantization=False):

@@ -224,9 +224,10 @@ class UNetPlan(Emitter):
 
     # ---- host-facing helpers
     def close(self):
-        """Releases the graphs (and the DDIM edit buffers) of the sampler states attached to this plan (ddim.py / plms.py
-        fast paths)."""
-        for attr in ("_sampler_state", "_sampler_state_cfg", "_plms_state", "_plms_state_cfg", "_ddpm_state"):
+        """Releases the graphs (and the DDIM edit buffers) of the sampler states attached to this plan (ddim.py / plms.py /
+        dpm_solver.py fast paths)."""
+        for attr in ("_sampler_state", "_sampler_state_cfg", "_plms_state", "_plms_state_cfg", "_ddpm_state",
+                     "_dpm_state", "_dpm_state_cfg"):
             st = self.__dict__.pop(attr, None)
             if st is not None:
                 st.close()
@@ -609,19 +610,24 @@ class SamplerState:
     "masked" = the same kernel with the keep table and the mask (inpainting).  Each has graphs of its own.  A chain
     that starts at loop position k > 0 only presets plan.step to k: timestep rows and coefficients stay the S-row tables."""
 
-    def __init__(self, plan: UNetPlan, channels, cfg=False, plms=False, ddpm=False):
+    def __init__(self, plan: UNetPlan, channels, cfg=False, plms=False, ddpm=False, dpm=False):
         """cfg: classifier-free guidance — the plan runs 2*B rows ([unconditional ; conditional], ddim.py:173-178),
         the latent state has B = plan.B // 2 samples and the update combines the two halves of eps.
         plms: the graph is one PLMS model evaluation (upk_plms_step_f32; plan rows = evaluations = steps + 1).
         ddpm: the graph is one DDPM ancestral step (upk_ddpm_step_f32; plan rows = timesteps of the chain, coefficient
         rows of 8).  Its posterior noise table [rows, n] is always there, and a masked chain adds the q_sample noise
-        table, x0 and the expanded mask: at B = 8, 32x24 and 1000 steps each table is 1000 * 24576 * 4 B = 98 MB."""
+        table, x0 and the expanded mask: at B = 8, 32x24 and 1000 steps each table is 1000 * 24576 * 4 B = 98 MB.
+        dpm: the graph is one DPM-Solver++(2M) step (upk_dpmpp_2m_step_f32; coefficient rows of 8, guidance allowed); x0_old
+        [n] is the data prediction of the step before, which the kernel reads on second-order rows only, so nothing
+        initialises it."""
         require(plan.mode == "sampler", "SamplerState needs a sampler-mode plan", ValueError)
         self.plan = plan
         self.cfg = bool(cfg)
         self.plms = bool(plms)
         require(not cfg or plan.B % 2 == 0, "guidance runs [uncond ; cond]: the plan's batch must be even", ValueError)
         require(not (ddpm and (cfg or plms)), "the DDPM step has no guidance and no PLMS history", ValueError)
+        require(not (dpm and (plms or ddpm)), "the DPM-Solver++ step is a sampler state of its own", ValueError)
+        self.dpm = bool(dpm)
         self.ddpm = bool(ddpm)
         self.ddpm_flags, self.masked = 0, False  # (the DDPM variant the next graph() / step_eager() runs)
         self.noise2 = self.x0 = self.mask = None
@@ -632,11 +638,12 @@ class SamplerState:
         self.C = channels
         self.x = plan.alloc(B, channels, H, W, dtype=torch.float32)
         self.pred_x0 = plan.alloc(B, channels, H, W, dtype=torch.float32)
-        self.coefs = plan.alloc(R, 8 if ddpm else 4, dtype=torch.float32)
+        self.coefs = plan.alloc(R, 8 if (ddpm or dpm) else 4, dtype=torch.float32)
         self.noise = None
         self.graphs = {}
         self.step_done = plan.alloc(1, dtype=torch.int32, zero=True)  # arrival counter of the step kernels
         self.hist = plan.alloc(3, B * channels * H * W, dtype=torch.float32) if plms else None
+        self.x0_old = plan.alloc(B * channels * H * W, dtype=torch.float32) if dpm else None
 
     def close(self):
         """Destroys the instantiated HIP graphs (they hold device memory; called when the owning plan is dropped).
@@ -694,6 +701,12 @@ class SamplerState:
                                                ptr(self.noise2), ptr(self.x0), ptr(self.mask), p.step.data_ptr(),
                                                self.pred_x0.data_ptr(), p.xin.t.data_ptr(), p.xin.ld, self.B, self.C,
                                                p.H * p.W, int(self.ddpm_flags), stream))
+        elif self.dpm:
+            require(nz is None, "DPM-Solver++(2M) runs with eta = 0", ValueError)
+            p.ctx._chk(p.lib.upk_dpmpp_2m_step_f32(p.hctx, self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(),
+                                                   p.step.data_ptr(), self.x0_old.data_ptr(), self.pred_x0.data_ptr(),
+                                                   p.xin.t.data_ptr(), p.xin.ld, self.B, self.C, p.H * p.W, 0,
+                                                   float(scale), int(self.cfg), stream))
         elif self.plms:
             require(nz is None, "PLMS runs with eta = 0", ValueError)
             p.ctx._chk(p.lib.upk_plms_step_f32(p.hctx, self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(),
@@ -730,7 +743,7 @@ class SamplerState:
         if self.ddpm:
             key += ("ddpm", int(self.ddpm_flags), bool(self.masked))
         elif self.edit is not None:
-            require(self.edit in ("plain", "masked") and not self.plms, "edit mode is 'plain' or 'masked', DDIM only",
+            require(self.edit in ("plain", "masked") and not (self.plms or self.dpm), "edit mode is 'plain' or 'masked', DDIM only",
                     ValueError)
             key += ("edit", self.edit)
         g = self.graphs.pop(key, None)

@@ -182,19 +182,21 @@ class InferenceModel:
                 batch[k] = [v] * repeat
         return batch
 
-    def generate(self, batch, steps=200, repeat=1, use_ema=True):
+    def generate(self, batch, steps=200, repeat=1, use_ema=True, sampler="ddim"):
         """log_images with the demo's settings -> {'reconstruction'?, 'samples'} as float numpy [b, h, w, 3] in [0, 1]
-        (:160-170; `repeat` is unused there as well)."""
+        (:160-170; `repeat` is unused there as well).  sampler: "ddim" (the reference's), or "dpmpp_2m" for
+        DPM-Solver++(2M) with `steps` steps (LatentDiffusion.sample_log)."""
+        extra = {} if sampler == "ddim" else {"sampler": sampler}
         with torch.no_grad():
             images = self.model.log_images(batch, ddim_steps=steps, use_ema=use_ema, unconditional_guidance_scale=3.,
-                                           unconditional_guidance_label=[""])
+                                           unconditional_guidance_label=[""], **extra)
         out = {}
         for k, v in images.items():
             v = torch.clamp(v.detach().cpu(), -1., 1.)
             out[k] = v.permute(0, 2, 3, 1).numpy() * 0.5 + 0.5
         return out
 
-    def upscale(self, pictures, styles, txt, steps=200, pad=(4, 0), use_ema=False, image=None):
+    def upscale(self, pictures, styles, txt, steps=200, pad=(4, 0), use_ema=False, image=None, sampler="ddim"):
         """The demo's "Upscale" button (app.py:387-399), called on the InferenceModel that holds the upscale checkpoint:
         low-resolution pictures -> generate()'s dict, 'samples' float numpy [B, f H, f W, 3] in [0, 1] with [H, W] the
         model's image_size and f = 2 ** num_downs (512 x 384 for the reference's config).
@@ -204,7 +206,7 @@ class InferenceModel:
         reference's lr_transform (pad 4 columns by edge replication, bilinear resize as Pillow does it, ToTensor,
         x * 2 - 1) in one launch on the device; batch['image'] defaults to zeros [B, f H, f W, 3], standing in for the
         dummy picture the demo loads (only its shape matters outside the reconstruction).  As with generate, log_images'
-        default N = 8 caps the samples of one call."""
+        default N = 8 caps the samples of one call.  sampler: as in generate."""
         from . import prepare
         if isinstance(pictures, (list, tuple)):
             pictures = np.stack([np.asarray(p.convert("RGB") if hasattr(p, "convert") else p, dtype=np.uint8) for p in pictures])
@@ -223,7 +225,7 @@ class InferenceModel:
             f = 2 ** self.model.num_downs
             image = torch.zeros(n, f * self.model.image_size[0], f * self.model.image_size[1], 3, device=lr.device)
         batch = {'image': image, 'lr': lr, 'styles': styles.to(lr.device), 'txt': txt}
-        return self.generate(batch, steps, use_ema=use_ema)
+        return self.generate(batch, steps, use_ema=use_ema, sampler=sampler)
 
     def extract_styles(self, picture, segm, segmenter='lip'):
         """The style crops of ONE source picture, ready for mix_style: fp32 [9, 3, 224, 224] on the device, one crop per

@@ -5,7 +5,8 @@ betas / alphas_cumprod in float64 numpy then stored fp32 (util.py:21-43, ddpm.py
 DDIM selection and sigmas per util.py:46-74.  The per-step scalars that the reference
 re-materialises with torch.full every step (ddim.py:189-192) are folded here into ONE
 device table of 4 fp32 coefficients per step for upk_ddim_step_f32 (8 per step for the DDPM
-step, upk_ddpm_step_f32).
+step, upk_ddpm_step_f32, and for the DPM-Solver++(2M)
+step, upk_dpmpp_2m_step_f32).
 """
 import numpy as np
 import torch
@@ -58,6 +59,54 @@ def ddim_coefficient_table(alphas, alphas_prev, sigmas, sqrt_one_minus_alphas, o
     idx = torch.as_tensor(np.asarray(order), dtype=torch.long)
     a, ap, sg, sq = a[idx], ap[idx], sg[idx], sq[idx]
     return torch.stack([sq, 1.0 / a.sqrt(), ap.sqrt(), (1.0 - ap - sg ** 2).sqrt()], dim=1).contiguous()
+
+
+def make_logsnr_timesteps(alphas_cumprod, S):
+    """S + 1 integer timesteps `node`, ascending from 0 to T - 1, uniform in lambda = log(alpha / sigma) (half the logSNR)
+    as far as integers allow — the grid DPM-Solver++ is derived on: node[k] is the first t nearest to
+    lam[0] + (lam[T-1] - lam[0]) * k / S, then made strictly increasing in one ascending pass.  In the DDIM tables:
+    ddim_timesteps = node[1:], alphas = acp[node[1:]], alphas_prev = acp[node[:-1]] (the last target is acp[0], as DDIM's)."""
+    acp = np.asarray(torch.as_tensor(alphas_cumprod).detach().cpu().numpy(), dtype=np.float64)
+    T, S = int(acp.shape[0]), int(S)
+    if S < 1:
+        raise ValueError("make_logsnr_timesteps: S = %d, need at least one step" % S)
+    lam = 0.5 * np.log(acp / (1.0 - acp))
+    g = lam[0] + (lam[T - 1] - lam[0]) * np.arange(S + 1, dtype=np.float64) / S
+    node = np.abs(lam[None, :] - g[:, None]).argmin(axis=1).astype(np.int64)  # (argmin: the first minimiser)
+    for k in range(1, S + 1):
+        node[k] = max(node[k], node[k - 1] + 1)
+    if node[0] < 0 or node[-1] > T - 1:
+        raise ValueError("make_logsnr_timesteps: %d strictly increasing steps do not fit into %d timesteps" % (S, T))
+    return node
+
+
+def dpm_coefficient_table(alphas, alphas_prev, order=2, lower_order_final=None):
+    """[S, 8] fp32 rows of upk_dpmpp_2m_step_f32 in LOOP order (descending DDIM index) from the DDIM tables `alphas` /
+    `alphas_prev` (ascending index, as DDIMSampler keeps them).  Row i, step t -> p with alpha = sqrt(a), sigma = sqrt(1 - a),
+    lambda = log(alpha / sigma), h_i = lambda_p - lambda_t > 0:
+        {sigma_t, 1 / alpha_t, sigma_p / sigma_t, -alpha_p * expm1(-h_i), w_i, 0, 0, 0}
+    w_i = h_i / (2 h_{i-1}) (= 1 / (2 r_i)) on a second-order row; 0 on a first-order one: row 0, every row with order = 1,
+    and the last row with lower_order_final (default: S < 15, the usual rule for few steps).  Computed in fp64 and rounded
+    once."""
+    if order not in (1, 2):
+        raise ValueError("dpm_coefficient_table: order %r (1 or 2)" % (order,))
+    f64 = lambda v: np.asarray(torch.as_tensor(v).detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float64)
+    a_t, a_p = f64(alphas)[::-1], f64(alphas_prev)[::-1]
+    S = int(a_t.shape[0])
+    if lower_order_final is None:
+        lower_order_final = S < 15
+    al_t, sg_t, al_p, sg_p = np.sqrt(a_t), np.sqrt(1.0 - a_t), np.sqrt(a_p), np.sqrt(1.0 - a_p)
+    h = np.log(al_p / sg_p) - np.log(al_t / sg_t)
+    if not (h > 0).all():
+        raise ValueError("dpm_coefficient_table: the logSNR must rise along the chain")
+    w = np.zeros(S)
+    if order == 2:
+        w[1:] = h[1:] / (2.0 * h[:-1])
+        if lower_order_final:
+            w[-1] = 0.0
+    rows = np.zeros((S, 8))
+    rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3], rows[:, 4] = sg_t, 1.0 / al_t, sg_p / sg_t, -al_p * np.expm1(-h), w
+    return torch.from_numpy(rows.astype(np.float32)).contiguous()
 
 
 def ddpm_coefficient_table(model, t_order):
