@@ -793,6 +793,42 @@ int upk_clip_normalize_u8(upk_ctx* ctx, const uint8_t* src, long long pitch, lon
                           int n, int h, int w, const float* mean_std_host, float* dst, upk_stream stream);
 
 /* ------------------------------------------------------------------ */
+/* Pose interpolation: the conditioning of a frame sequence.             */
+/* ------------------------------------------------------------------ */
+/* The "Interpolate" loop of the reference's demo (app.py:280-308 with get_coord / get_mask / interp_mask, app.py:158-183)
+ * for all n frames in ONE launch, one workgroup per frame.  DESIGN.md 31.
+ *   src_mask, dst_mask   DEVICE fp32 dense [h, w]: the person_mask of the source and of the destination pose
+ *   src_smpl, dst_smpl   DEVICE fp32 [d]
+ *   alphas     DEVICE double [n]: frame i is alpha_i of the source and 1 - alpha_i of the destination.  Read by the
+ *              kernel, so a captured launch follows a rewritten buffer.
+ *   mask_out   DEVICE fp32 dense [n, 1, h, w];  smpl_out  DEVICE fp32 dense [n, d]
+ *   boxes      may be NULL: DEVICE int32 [n + 2][4] = (r0, r1, c0, c1), inclusive; row 0 the source's box, row 1 the
+ *              destination's, row 2 + i frame i's
+ * Box of a map: r0 / r1 = the first / last row holding an OCCUPIED element, c0 / c1 likewise for columns; an element is
+ * occupied when it is neither -1 nor 0.  PRECONDITION: the reference takes the rows and columns whose fp32 mean is
+ * non-zero after -1 was replaced by 0; the two agree for every map whose other entries share one sign ({-1, -0.99215686},
+ * {-1, 1}, and those after the reference's in-place zeroing: every mask this project or the demo makes).  numpy's
+ * summation order is not emulated, so a map with entries of both signs that cancel in a row's mean is outside the contract.
+ * Each workgroup reduces both maps in LDS with integer minima and maxima (no order to depend on), then writes its frame.
+ * Arithmetic, one correctly rounded IEEE operation at a time, never a fused multiply-add:
+ *   beta = 1.0 - alpha                                                     in fp64
+ *   box_i[k] = (int)(fl64(fl64(alpha * src_box[k]) + fl64(beta * dst_box[k])))   truncation toward zero; numpy's
+ *              (alpha * c1 + (1 - alpha) * c2).astype(np.int32).  NOT "fixed": alpha = 0.05 on rows 3 and 3 gives 2.
+ *   smpl_out[i][j] = fl32(fl32((float)alpha * src_smpl[j]) + fl32((float)beta * dst_smpl[j]))   torch's alpha * x + (1 - alpha) * y
+ *              with a float64 scalar alpha and fp32 tensors
+ *   mask_out[i][0][y][x] = -0.99215686 (= fl(fl(1 / 255) * 2 - 1)) for r0 <= y <= r1 and c0 <= x <= c1 of box_i, else -1
+ * A frame's box is clamped to the map (lower bounds to [0, size], upper bounds to [-1, size - 1]); a box with min > max
+ * writes no foreground.  With alpha in [0, 1] the clamp never acts.  When either map has no occupied element its row of
+ * `boxes` and every frame's row are -1, -1, -1, -1 and every frame is all background (the reference raises IndexError).
+ * Inputs are not modified.  Errors (UPK_EINVAL): a null pointer other than boxes, non-positive sizes, fp32 / int32
+ * pointers not 4-byte or alphas not 8-byte aligned, an output that overlaps an input or another output; UPK_ESHAPE:
+ * n > 65535, a map of 2^31 elements or more.  Nothing is launched on an error.  One launch, class "other".  Never
+ * allocates, never synchronises, graph-capturable. */
+int upk_pose_interp_f32(upk_ctx* ctx, const float* src_mask, const float* dst_mask, int h, int w, const float* src_smpl,
+                        const float* dst_smpl, int d, const double* alphas, int n, float* mask_out, float* smpl_out,
+                        int32_t* boxes, upk_stream stream);
+
+/* ------------------------------------------------------------------ */
 /* SSIM / MS-SSIM moments of uint8 picture pairs (evaluation metrics).   */
 /* ------------------------------------------------------------------ */
 /* The per-image arithmetic of scripts/eval_metrics.py:110-111 (pytorch_msssim.ssim / ms_ssim with data_range=1,

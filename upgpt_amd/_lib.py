@@ -30,6 +30,7 @@ SYMBOLS = [
     "upk_patchify_nchw_f32_f16", "upk_vit_assemble_f16", "upk_gather_rows_f16",
     "upk_image_finish_u8", "upk_resize_bilinear_u8", "upk_segm_boxes_u8", "upk_style_crops_u8",
     "upk_cond_bbox_u8", "upk_cond_gather_u8", "upk_cond_smpl_u8", "upk_clip_normalize_u8", "upk_ssim_ws_bytes", "upk_ssim_u8",
+    "upk_pose_interp_f32",
     "upk_lpips_input_f16", "upk_relu_pool_nhwc_f16", "upk_lpips_ws_bytes", "upk_lpips_layer_f16",
     "upk_conv2d_rect_f16", "upk_pool3_nhwc_f16", "upk_fid_input_f16", "upk_avgpool_global_f32",
     "upk_q_sample_f32", "upk_p_losses_ws_bytes", "upk_p_losses_f32",
@@ -210,6 +211,7 @@ def load_library(path=None):
             "upk_cond_gather_u8": (C.c_int, [vp, vp, i64, i64, i32, i32, i32, vp, vp, i32, i32, C.POINTER(C.c_float), vp, vp]),
             "upk_cond_smpl_u8": (C.c_int, [vp, vp, i64, i64, i32, i32, i32, vp, vp]),
             "upk_clip_normalize_u8": (C.c_int, [vp, vp, i64, i64, vp, i32, i32, i32, C.POINTER(C.c_float), vp, vp]),
+            "upk_pose_interp_f32": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]),
             "upk_ssim_ws_bytes": (C.c_size_t, [i32, i32, i32, i32]),
             "upk_ssim_u8": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, vp, vp, C.c_size_t, vp]),
             "upk_lpips_input_f16": (C.c_int, [vp, vp, i32, i64, i64, i32, i32, i32, i32, C.POINTER(C.c_float), vp, i64, vp]),
@@ -468,6 +470,13 @@ class Context:
         ms = None if mean_std is None else (C.c_float * 6)(*[float(v) for v in mean_std])
         self._chk(self.lib.upk_clip_normalize_u8(self.h, _ptr(src), int(pitch), int(ss), _ptr(valid), int(n), int(h), int(w), ms,
                                                  _ptr(dst), self._s()))
+
+    def pose_interp(self, src_mask, dst_mask, h, w, src_smpl, dst_smpl, d, alphas, n, mask_out, smpl_out, boxes=None):
+        """upk_pose_interp_f32: alphas device float64 [n] -> mask_out [n, 1, h, w], smpl_out [n, d], boxes int32 [n + 2, 4]
+        (may be None)."""
+        self._chk(self.lib.upk_pose_interp_f32(self.h, _ptr(src_mask), _ptr(dst_mask), int(h), int(w), _ptr(src_smpl),
+                                               _ptr(dst_smpl), int(d), _ptr(alphas), int(n), _ptr(mask_out), _ptr(smpl_out),
+                                               _ptr(boxes), self._s()))
 
     def ssim_ws_bytes(self, batch, h, w, levels):
         return self.lib.upk_ssim_ws_bytes(int(batch), int(h), int(w), int(levels))

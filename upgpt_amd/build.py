@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.environ.get("UPK_LIB") or os.path.join(HERE, "libupk.so")  # (UPK_LIB + UPK_CXXFLAGS: dev builds)
 SOURCES = ["igemm.hip", "bigtile.hip", "astat.hip", "mlp.hip", "xblock.hip", "attention.hip", "norm.hip", "misc.hip", "image.hip",
-           "metrics.hip", "lpips.hip", "inception.hip", "resize.hip", "styles.hip", "batch.hip", "loss.hip", "cond.hip", "rng.hip", "dpm.hip"]
+           "metrics.hip", "lpips.hip", "inception.hip", "resize.hip", "styles.hip", "batch.hip", "loss.hip", "cond.hip", "rng.hip", "dpm.hip", "pose.hip"]
 # per-file flags.  attention.hip: MFMA results straight into arch VGPRs — the softmax between the two matmuls reads
 # every score with VALU instructions, and with the accumulators in AGPRs 112 of ~600 issue slots per 64-key tile were
 # v_accvgpr moves (the kernels use < 128 registers, there is nothing to gain from the AGPR file)
@@ -32,11 +32,13 @@ SOURCES = ["igemm.hip", "bigtile.hip", "astat.hip", "mlp.hip", "xblock.hip", "at
 # (r + g + b) / 3; (u / 255 - mean) / std)
 # loss.hip: upk_q_sample_f32 and the element terms of upk_p_losses_f32 likewise (a * x0, s * n, +; t - p, d * d, w * e)
 # rng.hip: the normal transform of upk_randn_keyed_f32 likewise (-2 * log, r * cos, r * sin, z * scale)
+# pose.hip: the box blend (fp64) and the SMPL blend (fp32) of upk_pose_interp_f32 likewise (a * x, b * y, +)
 FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans", "-mno-amdgpu-ieee"],
               "image.hip": ["-ffp-contract=off"], "lpips.hip": ["-ffp-contract=off"],
               "inception.hip": ["-ffp-contract=off"], "resize.hip": ["-ffp-contract=off"],
               "styles.hip": ["-ffp-contract=off"], "batch.hip": ["-ffp-contract=off"],
-              "loss.hip": ["-ffp-contract=off"], "rng.hip": ["-ffp-contract=off"]}
+              "loss.hip": ["-ffp-contract=off"], "rng.hip": ["-ffp-contract=off"],
+              "pose.hip": ["-ffp-contract=off"]}
 ARCH = "gfx950"
 
 

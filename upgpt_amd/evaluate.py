@@ -18,6 +18,9 @@ shards.
 
 run_upscale is the second model's pass over a results tree: results/samples-sized pictures -> the `lr` conditioning on the
 device (upgpt_amd/prepare.py, upk_resize_bilinear_u8) -> the upscale model -> results/upscaled.
+
+run_interpolation is the demo's "Interpolate" flow: InferenceModel.interpolate -> interp/interp_{i}.jpg, interp_strip.jpg
+and, with an upscale model, interp_upscaled/interp_{i}.png.
 """
 import os
 from pathlib import Path
@@ -630,6 +633,40 @@ def run_upscale(model, batches, lr_dir, save_dir, pad=(8, 0), lanes=1, noise_see
     else:
         _run_lanes(model, work(), lanes, step)
     return Path(save_dir) / "results"
+
+
+def run_interpolation(im, batch, dst_pose, alphas, save_dir, steps=200, sampler="ddim", noise_seed=0, upscale=None, txt=None):
+    """The demo's "Interpolate" flow (app.py:280-308) as one call: im.interpolate(batch, dst_pose, alphas, steps=steps,
+    sampler=sampler, noise_seed=noise_seed) — `im` an InferenceModel, `batch` its un-batched sample with the source pose,
+    `dst_pose` prepare.load_pose's dict; with the default seed every frame meets the same keyed noise, noise_seed=None
+    draws from the torch generator as the reference does — and then
+      <save_dir>/interp/interp_{i}.jpg   every frame exactly as the app writes it: Image.fromarray(np.uint8(sample * 255))
+      <save_dir>/interp_strip.jpg        the frames side by side, left to right in the order of `alphas`
+    upscale (an InferenceModel holding the upscale checkpoint): the frames' bytes (those in memory, not the decoded JPEG
+    files) go through upscale.upscale(frames, batch['styles'], txt, steps=steps, sampler=sampler) in chunks of 8, its cap
+    per call, and are written as <save_dir>/interp_upscaled/interp_{i}.png; txt defaults to batch['txt'].
+    Returns the list of the frames' paths (the .jpg files), in frame order."""
+    from PIL import Image
+    save_dir = Path(save_dir)
+    out = im.interpolate(batch, dst_pose, alphas, steps=steps, sampler=sampler, noise_seed=noise_seed)
+    frames = [np.uint8(sample * 255) for sample in out["samples"]]
+    os.makedirs(str(save_dir / "interp"), exist_ok=True)
+    paths = []
+    for i, frame in enumerate(frames):
+        paths.append(save_dir / "interp" / f"interp_{i}.jpg")
+        Image.fromarray(frame).save(paths[-1])
+    Image.fromarray(np.concatenate(frames, axis=1)).save(save_dir / "interp_strip.jpg")
+    if upscale is not None:
+        os.makedirs(str(save_dir / "interp_upscaled"), exist_ok=True)
+        text = batch["txt"] if txt is None else txt
+        cap = 8
+        for lo in range(0, len(frames), cap):
+            big = upscale.upscale(np.stack(frames[lo:lo + cap]), batch["styles"], text, steps=steps, sampler=sampler)["samples"]
+            require(len(big) == len(frames[lo:lo + cap]), "run_interpolation: upscale returned %d pictures for %d frames" % (
+                len(big), len(frames[lo:lo + cap])), ValueError)
+            for j, sample in enumerate(big):
+                Image.fromarray(np.uint8(sample * 255)).save(save_dir / "interp_upscaled" / f"interp_{lo + j}.png")
+    return paths
 
 
 def run_styles(image_root, segm_root, dst_root, segmenter='mm', batch_size=16):

@@ -182,11 +182,14 @@ class InferenceModel:
                 batch[k] = [v] * repeat
         return batch
 
-    def generate(self, batch, steps=200, repeat=1, use_ema=True, sampler="ddim"):
+    def generate(self, batch, steps=200, repeat=1, use_ema=True, sampler="ddim", noise_keys=None):
         """log_images with the demo's settings -> {'reconstruction'?, 'samples'} as float numpy [b, h, w, 3] in [0, 1]
         (:160-170; `repeat` is unused there as well).  sampler: "ddim" (the reference's), or "dpmpp_2m" for
-        DPM-Solver++(2M) with `steps` steps (LatentDiffusion.sample_log)."""
+        DPM-Solver++(2M) with `steps` steps (LatentDiffusion.sample_log).  noise_keys (upgpt_amd.rng.NoiseKeys, one key
+        per sample): handed to log_images, which then draws keyed noise instead of the torch generator's."""
         extra = {} if sampler == "ddim" else {"sampler": sampler}
+        if noise_keys is not None:
+            extra["noise_keys"] = noise_keys
         with torch.no_grad():
             images = self.model.log_images(batch, ddim_steps=steps, use_ema=use_ema, unconditional_guidance_scale=3.,
                                            unconditional_guidance_label=[""], **extra)
@@ -195,6 +198,47 @@ class InferenceModel:
             v = torch.clamp(v.detach().cpu(), -1., 1.)
             out[k] = v.permute(0, 2, 3, 1).numpy() * 0.5 + 0.5
         return out
+
+    FRAMES_PER_CALL = 8  # log_images' default N: the samples one generate() call returns at most
+
+    def interpolate(self, batch, dst_pose, alphas, steps=200, use_ema=True, sampler="ddim", noise_seed=None, noise="shared"):
+        """The demo's "Interpolate" button (app.py:280-308): n = len(alphas) frames between the pose of `batch` and
+        `dst_pose`, frame i conditioned on alphas[i] of the source and 1 - alphas[i] of the destination -> generate's
+        dict ('samples', 'reconstruction'?) with ALL n frames, float numpy [n, h, w, 3] in [0, 1].
+        batch: the UN-batched sample the demo hands to create_batch (image, styles, txt, ...), with the source pose's
+        `smpl` [1, d] and `person_mask` [1, h, w]; dst_pose: prepare.load_pose's dict, or any dict with `smpl` and
+        `person_mask`.  alphas: floats in [0, 1] (ValueError otherwise, also for none at all).
+        The conditioning of all frames is one launch on the device (prepare.interp_pose), bit for bit the reference's
+        loop.  The frames are then produced in chunks of at most 8, log_images' cap N: the reference makes ONE generate
+        call, so the demo's default of nine alphas silently yields eight pictures there, and nine here.
+        noise_seed=None draws x_T and the step noise from the torch generator, independently per frame, as the reference
+        does.  With a seed the frames are keyed (upgpt_amd.rng.NoiseKeys(noise_seed, ids)): noise="shared" gives every
+        frame id 0, so x_T and every step's noise are the same for all frames and only the pose differs between them;
+        noise="independent" gives frame i id i.
+        Neither `batch` nor `dst_pose` is modified.  (The reference's get_coord zeroes the destination mask's background
+        in place when that mask is a CPU tensor; this has no effect on any result and is not reproduced.)"""
+        from . import prepare
+        from ._check import require
+        from .rng import NoiseKeys
+        a = prepare.check_alphas(alphas)
+        require(noise in ("shared", "independent"), lambda: "noise must be 'shared' or 'independent', got %r" % (noise,), ValueError)
+        for name, d in (("batch", batch), ("dst_pose", dst_pose)):
+            for k in ("smpl", "person_mask"):
+                require(k in d, lambda: "interpolate: %s has no %r" % (name, k), ValueError)
+        n = int(a.size)
+        cond = prepare.interp_pose(batch["person_mask"], dst_pose["person_mask"], batch["smpl"], dst_pose["smpl"], a)
+        keys = None
+        if noise_seed is not None:
+            keys = NoiseKeys(noise_seed, [0] * n if noise == "shared" else range(n), device=self.device)
+        rest = {k: v for k, v in batch.items() if k not in ("smpl", "person_mask")}
+        parts = []
+        for lo in range(0, n, InferenceModel.FRAMES_PER_CALL):
+            m = min(InferenceModel.FRAMES_PER_CALL, n - lo)
+            chunk = InferenceModel.create_batch(self, dict(rest), repeat=m)  # (a copy of the dict: `batch` keeps its entries)
+            chunk["smpl"], chunk["person_mask"] = cond["smpl"][lo:lo + m], cond["person_mask"][lo:lo + m]
+            kw = {} if keys is None else {"noise_keys": keys[lo:lo + m]}
+            parts.append(InferenceModel.generate(self, chunk, steps, use_ema=use_ema, sampler=sampler, **kw))
+        return {k: np.concatenate([p[k] for p in parts], axis=0) for k in parts[0]}
 
     def upscale(self, pictures, styles, txt, steps=200, pad=(4, 0), use_ema=False, image=None, sampler="ddim"):
         """The demo's "Upscale" button (app.py:387-399), called on the InferenceModel that holds the upscale checkpoint:

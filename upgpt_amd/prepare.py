@@ -151,3 +151,127 @@ def lr_transform(pictures, size, pad=(0, 0), out_u8=None):
     bytes from the same launch."""
     _, nchw, nhwc = _launch(pictures, size, pad, False, True, out_u8)
     return nchw, nhwc
+
+
+# ---- pose interpolation (DESIGN.md 31): the conditioning of a frame sequence and the demo's pose folders
+
+def check_alphas(alphas):
+    """`alphas` as a float64 array [n]; ValueError for an empty sequence, a NaN or a value outside [0, 1] (outside it the
+    reference's negative slice bounds wrap around, which is not worth reproducing)."""
+    try:
+        a = np.array(alphas, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError("alphas must be a sequence of floats, got %r" % (alphas,))
+    require(a.size >= 1, "alphas must not be empty", ValueError)
+    require(not np.isnan(a).any(), "alphas holds a NaN", ValueError)
+    require(bool((a >= 0.0).all() and (a <= 1.0).all()), lambda: "alphas must lie in [0, 1], got %s" % (a.tolist(),), ValueError)
+    return a
+
+
+def _pose_f32(t, name, tail_dims):
+    """fp32 tensor whose leading axes are all 1 and whose last `tail_dims` axes are the payload, dense; never a view the
+    caller's tensor could be written through."""
+    if isinstance(t, np.ndarray):
+        t = torch.from_numpy(np.array(t))
+    require(torch.is_tensor(t), "%s must be an fp32 tensor or array, got %s" % (name, type(t).__name__), TypeError)
+    require(t.dtype == torch.float32, "%s must be fp32, got %s" % (name, t.dtype), TypeError)
+    require(t.dim() >= tail_dims and t.numel() >= 1 and all(int(s) == 1 for s in t.shape[:t.dim() - tail_dims]),
+            "%s must be %s with leading axes of 1, got %s" % (name, "[1, h, w]" if tail_dims == 2 else "[1, d]", tuple(t.shape)),
+            ValueError)
+    return t.reshape(t.shape[t.dim() - tail_dims:]).contiguous()
+
+
+def interp_pose(src_mask, dst_mask, src_smpl, dst_smpl, alphas, return_boxes=False):
+    """The conditioning of the n = len(alphas) frames of a pose interpolation, the loop of app.py:298-300, in ONE
+    upk_pose_interp_f32 launch on the current stream: {'smpl': fp32 [n, 1, d], 'person_mask': fp32 [n, 1, h, w]} on the
+    device, frame i being alphas[i] of the source and 1 - alphas[i] of the destination — bit for bit torch's
+    `alpha * smpl_src + (1 - alpha) * smpl_dst` and inference.interp_mask(src_mask, dst_mask, alpha) with a numpy float64
+    alpha (include/upk.h states the arithmetic and the occupancy precondition on the masks).
+    src_mask, dst_mask: fp32 [1, h, w] of one size; src_smpl, dst_smpl: fp32 [1, d]; host tensors / arrays are uploaded,
+    device tensors are read in place, none is modified.  alphas: any float sequence, taken as float64 and uploaded once;
+    ValueError for an empty one, a NaN or a value outside [0, 1].
+    A HOST mask without foreground (no element other than -1 and 0) raises ValueError before anything is uploaded, where
+    the reference raises IndexError; a DEVICE mask is not looked at (that would synchronise): the kernel then gives every
+    frame an all-background mask and boxes of -1.
+    return_boxes=True adds 'boxes': int32 [n + 2, 4] = (r0, r1, c0, c1) on the device, rows 0 and 1 the source's and the
+    destination's box, row 2 + i frame i's.  No CPU fallback: without a GPU this raises."""
+    a = check_alphas(alphas)
+    sm, dm = _pose_f32(src_mask, "src_mask", 2), _pose_f32(dst_mask, "dst_mask", 2)
+    ss, ds = _pose_f32(src_smpl, "src_smpl", 1), _pose_f32(dst_smpl, "dst_smpl", 1)
+    require(sm.shape == dm.shape, "src_mask %s and dst_mask %s differ in size" % (tuple(sm.shape), tuple(dm.shape)), ValueError)
+    require(ss.shape == ds.shape, "src_smpl %s and dst_smpl %s differ in size" % (tuple(ss.shape), tuple(ds.shape)), ValueError)
+    for name, m in (("src_mask", sm), ("dst_mask", dm)):
+        if not m.is_cuda:
+            require(bool(((m != -1.0) & (m != 0.0)).any()), "%s has no foreground: its bounding box is undefined" % name, ValueError)
+    dev = next((t.device for t in (sm, dm, ss, ds) if t.is_cuda), None)
+    if dev is None:
+        require(torch.cuda.is_available(), "the frames are built on the MI355X (upk_pose_interp_f32): no GPU is visible and "
+                "there is no CPU fallback for the HIP path", RuntimeError)
+        dev = torch.device("cuda", torch.cuda.current_device())
+    with _lib.host_io():
+        sm, dm, ss, ds = (t.to(dev) for t in (sm, dm, ss, ds))
+        at = torch.from_numpy(a).to(dev)
+    n, (h, w), d = int(a.size), (int(v) for v in sm.shape), int(ss.shape[0])
+    mask = torch.empty((n, 1, h, w), dtype=torch.float32, device=dev)
+    smpl = torch.empty((n, 1, d), dtype=torch.float32, device=dev)
+    boxes = torch.empty((n + 2, 4), dtype=torch.int32, device=dev) if return_boxes else None
+    with torch.cuda.device(dev):
+        _lib.get_context(dev).pose_interp(sm, dm, h, w, ss, ds, d, at, n, mask, smpl, boxes)
+    out = {'smpl': smpl, 'person_mask': mask}
+    if return_boxes:
+        out['boxes'] = boxes
+    return out
+
+
+def read_pose_folder(folder):
+    """The host part of load_pose: (smpl fp32 array [1, 85] = pose | betas | camera, picture uint8 [H, W, 3], mask uint8
+    [H, W], the palette indices of the mode-P PNG) of a pose folder of the demo.  A folder without exactly one .p, one
+    .jpg and one .png, a pickle of another structure or an unreadable picture raises ValueError."""
+    import pickle
+    from pathlib import Path
+
+    from PIL import Image
+    folder = Path(folder)
+    require(folder.is_dir(), "load_pose: %s is not a directory" % folder, ValueError)
+    files = {}
+    for ext in (".p", ".jpg", ".png"):
+        found = sorted(f for f in folder.iterdir() if f.is_file() and f.suffix == ext)
+        require(len(found) == 1, "load_pose: %s holds %d %s files, expected exactly one" % (folder, len(found), ext), ValueError)
+        files[ext] = found[0]
+    try:
+        with open(str(files[".p"]), "rb") as f:
+            first = pickle.load(f)[0]
+        pose, betas = np.asarray(first['pred_body_pose']), np.asarray(first['pred_betas'])
+        smpl = np.concatenate((pose, betas, np.expand_dims(np.asarray(first['pred_camera']), 0)), axis=1)
+    except Exception as e:
+        raise ValueError("load_pose: %s is not a list whose first entry holds pred_body_pose (1, 72), pred_betas (1, 10) "
+                         "and pred_camera (3,): %s" % (files[".p"], e))
+    require(smpl.ndim == 2 and smpl.shape[0] == 1, "load_pose: %s gives an SMPL vector of shape %s" % (files[".p"], smpl.shape),
+            ValueError)
+    try:
+        with Image.open(str(files[".jpg"])) as im:
+            picture = np.asarray(im.convert("RGB"), dtype=np.uint8)
+        with Image.open(str(files[".png"])) as im:
+            mask = np.asarray(im, dtype=np.uint8)  # (mode P: the palette indices, what ToTensor reads)
+    except Exception as e:
+        raise ValueError("load_pose: cannot read the pictures of %s: %s" % (folder, e))
+    require(mask.ndim == 2, "load_pose: %s is not a one-channel picture" % files[".png"], ValueError)
+    return np.ascontiguousarray(smpl, dtype=np.float32), picture, mask
+
+
+def load_pose(folder, mask_size=(32, 24), crop=(256, 192)):
+    """The demo's load_smpl (app.py:115-143) of a pose folder (one .p, one .jpg, one .png):
+    'smpl'         fp32 [1, 85] host tensor: pred_body_pose | pred_betas | pred_camera of the pickle's first entry
+    'smpl_image'   uint8 [crop_h, crop_w, 3] host tensor: T.CenterCrop(crop) of the picture (the reference keeps the PIL
+                   picture; a picture smaller than the crop raises ValueError instead of being zero-padded)
+    'person_mask'  fp32 [1, h, w] on the device, mask_size = [h, w]: Pillow's NEAREST resize of the mode-P mask, ToTensor,
+                   x * 2 - 1, values {-1, -0.99215686} — the loader's input_mask_type='mask' path (data.person_mask:
+                   the same index tables, the same look-up table, one upk_cond_gather_u8 launch).
+    The pickle is read with pickle and numpy only.  The dict goes into InferenceModel.create_batch / interpolate as it is."""
+    from . import data
+    from .evaluate import center_crop_window
+    smpl, picture, mask = read_pose_folder(folder)
+    top, left, ch, cw = center_crop_window(picture.shape[0], picture.shape[1], list(crop))
+    person_mask = data.person_mask(mask[None], mask_size, 'mask')[0]
+    return {'smpl': torch.from_numpy(smpl), 'smpl_image': torch.from_numpy(np.array(picture[top:top + ch, left:left + cw])),
+            'person_mask': person_mask}
