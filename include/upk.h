@@ -371,7 +371,9 @@ const char* upk_conv_config_name(int cfg);
 /* ------------------------------------------------------------------ */
 /* q  : fp16 [B, n_q , ldq ] head h at columns [h*d, (h+1)*d)
  * k  : fp16 [B, n_kv, ldk ] same head layout, batch stride = k_batch_stride elements
- * vt : fp16 [B, heads, d, vt_ld] (V transposed, vt_ld >= round_up(n_kv,32), zero padded)
+ * vt : fp16 [B, heads, d, vt_ld] (V transposed, vt_ld >= round_up(n_kv,32); the key columns
+ *      [n_kv, round_up(n_kv,32)) of every row must hold zeros: a masked weight of 0 still
+ *      multiplies them; columns at or beyond round_up(n_kv,32) are never read)
  * out: fp16 [B, n_q , ldo ]
  * d in {32, 64, 128, 256, 512} (head dims are padded to these by weight packing). */
 int upk_attention_f16(upk_ctx* ctx, const void* q, int ldq, long long q_batch_stride,
@@ -399,6 +401,36 @@ int upk_attention_qproj_f16(upk_ctx* ctx, const void* x, int ldx, long long xbs,
                             const void* wq, const float* wq_colsum, const float* wq_bias, const void* k, int ldk,
                             long long kbs, const void* vt, int vt_ld, void* out, int ldo, long long obs, int batch,
                             int heads, int n_q, int n_kv, int d, float scale, upk_stream stream);
+
+/* Which kernel an attention launch runs.  The library compiles upk_attention_num_variants() instantiations:
+ * "direct32q1" ... "direct128q2" (head dim 32 / 64 / 128, one or two 16-query groups per wave), "direct256",
+ * "direct512", "lds32q1" ... "lds64q2" (K / V^T tiles of 64 keys staged in LDS), "wide512" (one head of 512 on
+ * LDS-shared 32-key tiles), "qproj32q2", "qproj64q1" (upk_attention_qproj_f16).  Indices are only ever appended.  The
+ * direct and qproj kernels run 1, 2 or 4 waves per workgroup, the lds and wide kernels 4.  A launch picks the variant
+ * and the waves per workgroup from the CU count, batch * heads and n_q (and, for wide512, from the strides and the
+ * alignment of the pointers); the queries below run the same decision procedure as the launch and enqueue nothing.
+ *
+ * upk_attention_plan: what upk_attention_f16 (causal = 0) / upk_attention_causal_f16 (causal = 1, n_q == n_kv) would
+ * run with these arguments (the launch's argument list as it stands; the stream is not used); the same errors as the
+ * launch.  upk_attention_qproj_plan: the same for
+ * upk_attention_qproj_f16 (the pointers do not enter its choice).
+ *
+ * upk_attention_override forces the variant and / or the waves per workgroup of the next launches of this context
+ * (tests and tuning): variant < 0 and wpb <= 0 restore the heuristic (variant 0 is a variant).  Precedence: the override,
+ * then the UPK_ATTN_* environment knobs, then the heuristic.  An override never bypasses what a kernel needs: the lds
+ * variants need n_kv % 64 == 0, n_kv >= 256, vt_ld % 8 == 0 and no causal mask; wide512 needs one head, n_kv % 32 == 0,
+ * ldk >= 512, ldq / ldk / vt_ld / batch strides % 8 == 0, 16-byte aligned q / k / vt and no causal mask; a variant runs
+ * only at its own head dim and through its own entry point; wpb is 1, 2 or 4, and 4 for the lds and wide variants.
+ * Anything else is refused (UPK_ESHAPE) before anything is launched, never approximated. */
+int upk_attention_num_variants(void);
+const char* upk_attention_variant_name(int variant);
+int upk_attention_override(upk_ctx* ctx, int variant, int wpb);
+int upk_attention_plan(upk_ctx* ctx, const void* q, int ldq, long long q_batch_stride, const void* k, int ldk,
+                       long long k_batch_stride, const void* vt, int vt_ld, const void* out, int ldo,
+                       long long o_batch_stride, int batch, int heads, int n_q, int n_kv, int d, float scale,
+                       upk_stream stream, int causal, int* variant, int* wpb);
+int upk_attention_qproj_plan(upk_ctx* ctx, int ldx, int cq, int ln_dim, int ldk, int vt_ld, int ldo, int batch, int heads,
+                             int n_q, int n_kv, int d, int* variant, int* wpb);
 
 /* Attention over a HANDFUL of keys: out = softmax(Q K^T * scale) V with 1 <= n_kv <= 16 — the cross-attention of
  * CLIPTextImageCrossAtten (ldm/modules/encoders/modules.py:259-323: 77 text tokens over 9 style embeddings, 8 heads

@@ -1,7 +1,7 @@
 """fp64 references with a derived, per-element error bound, for the dynamic-range tests.
 
-Every reference takes the fp16-rounded operands the kernel gets, computes the operation in fp64 on the CPU and returns
-``(ref, bound)``.  ``bound`` has the shape of ``ref`` and is the sum of the terms below; a kernel passes when
+Every reference takes the fp16-rounded operands the kernel gets, computes the operation in fp64 (on the CPU; the attention
+references also on the device that holds the operands) and returns ``(ref, bound)``.  ``bound`` has the shape of ``ref`` and is the sum of the terms below; a kernel passes when
 ``|got - ref| <= bound`` at every element (``ratio()`` returns max |got - ref| / bound, NaN counted as infinite).
 No term is fitted to a kernel: each follows from the number formats and the first-order error propagation.
 
@@ -39,7 +39,8 @@ e32 = 2^-24 (half an ulp of fp32, the rounding of one fp32 operation), E32 = 2^-
   The folded-LayerNorm GEMM y = (acc - mean u) rstd + b applies the GroupNorm / LayerNorm statistics terms to the two
   accumulations acc = x W'^T and u = sum_k W'_k (W' = fp16(W gamma)).
 
-The generators (``activations``) and the case tables are shared by the host and the GPU tests.
+The generators (``activations``) and the case tables are shared by the host and the GPU tests; ``attn_variant_rows`` is the
+table of every compiled attention instantiation and ``attn_layout`` the two operand layouts they are run in.
 """
 import math
 
@@ -282,7 +283,7 @@ def attention_ref(q, k, v, scale, causal=False, dq=None):
     logit = q @ k.transpose(-1, -2) * scale
     dl = scale * d * E32H * (q.abs() @ k.abs().transpose(-1, -2))
     if causal:
-        mask = torch.ones(q.shape[-2], nkv, dtype=torch.bool).triu(1)
+        mask = torch.ones(q.shape[-2], nkv, dtype=torch.bool, device=q.device).triu(1)
         logit = logit.masked_fill(mask, float("-inf"))
     m = logit.max(-1, keepdim=True).values
     p = torch.exp(logit - m)
@@ -451,18 +452,19 @@ def lngemm_case_ref(o):
     return linear_ref(d(o["x"]), W, bias=d(o["bf"]), act=o["act"], ln=(o["eps"], d(o["u"])))
 
 
-def attn_case(name, s):
-    """q, k scaled by sqrt(s) each (logits reach +-1e4 at 2^13), v by s; [B, n, heads * d] fp16."""
-    d, nq, nkv, causal = ATTN_CASES[name]
+def attn_case(name, s, shape=None, B=2, heads=2, device="cpu"):
+    """q, k scaled by sqrt(s) each (logits reach +-1e4 at 2^13), v by s; [B, n, heads * d] fp16.  shape = (d, nq, nkv,
+    causal), B, heads: a shape of the caller's instead of ATTN_CASES[name] (the name then only seeds the generator)."""
+    d, nq, nkv, causal = shape if shape is not None else ATTN_CASES[name]
     seed = sum(ord(ch) for ch in name)
     rs = math.sqrt(s)
     assert rs == int(rs) or s == 2 ** 13
     # sqrt(2^13) is not a power of two: 2^6 on q and 2^7 on k
     sq, sk = (2 ** 6, 2 ** 7) if s == 2 ** 13 else (int(rs), int(rs))
-    B, heads = 2, 2
     return dict(d=d, nq=nq, nkv=nkv, causal=causal, B=B, heads=heads, scale=d ** -0.5,
-                q=activations((B, nq, heads * d), seed, sq), k=activations((B, nkv, heads * d), seed + 1, sk),
-                v=activations((B, nkv, heads * d), seed + 2, s))
+                q=activations((B, nq, heads * d), seed, sq, device=device),
+                k=activations((B, nkv, heads * d), seed + 1, sk, device=device),
+                v=activations((B, nkv, heads * d), seed + 2, s, device=device))
 
 
 def attn_case_ref(o):
@@ -553,16 +555,16 @@ def mlp_case_ref(o):
 QPROJ = dict(C=224, heads=8, dh=28, nq=64, nkv=87)
 
 
-def qproj_case(s):
+def qproj_case(s, shape=None, B=2):
     """LayerNorm -> to_q -> q (fp16) -> cross-attention.  The normalisation makes q O(1) whatever the scale of x, so the
     scale goes to x (s), to k (sqrt(s), as in attn_case: logits of a few hundred, where one fp16 ulp of q still moves
-    them by less than one) and to v (s)."""
-    C, heads, dh, nq, nkv = (QPROJ[k] for k in ("C", "heads", "dh", "nq", "nkv"))
+    them by less than one) and to v (s).  shape: a dict with QPROJ's keys, instead of QPROJ."""
+    shape = dict(shape if shape is not None else QPROJ)
+    C, heads, dh, nq, nkv = (shape[k] for k in ("C", "heads", "dh", "nq", "nkv"))
     sk = 2 ** 7 if s == 2 ** 13 else int(math.sqrt(s))
-    B = 2
     return dict(B=B, s=s, x=norm_input((B, nq, C), 51, s), w=weights((heads * dh, C), C, 52), gamma=1 + vector(C, 53, 0.2),
                 beta=vector(C, 54), k=activations((B, nkv, heads, dh), 55, sk), v=activations((B, nkv, heads, dh), 56, s),
-                eps=1e-5, scale=dh ** -0.5, **QPROJ)
+                eps=1e-5, scale=dh ** -0.5, **shape)
 
 
 def qproj_case_ref(o):
@@ -572,6 +574,156 @@ def qproj_case_ref(o):
     q, dq = linear_ref(d(o["x"]).reshape(B * nq, -1), wf, bias=d(b), ln=(o["eps"], d(u)))
     sp = lambda t: t.reshape(B, nq, heads, dh).transpose(1, 2)
     return attention_ref(sp(q16(q)), d(o["k"]).transpose(1, 2), d(o["v"]).transpose(1, 2), o["scale"], dq=sp(dq))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# every compiled attention instantiation (upk_attention_variant_name) at the smallest shapes that reach each of its code
+# paths, and the two operand layouts they are run in.  Shared by tests/test_attention_variants_{host,gpu}.py.
+ATTN_VARIANT_SCALES = (1, 4, 2 ** 10)  # diffuse, peaked, near one-hot (attn_case's convention: sqrt(s) on q and k, s on v)
+ATTN_WPB = {"direct": (1, 2, 4), "qproj": (1, 2, 4), "lds": (4,), "wide": (4,)}  # waves per workgroup a family runs with
+ATTN_FILL = 7.0  # what `out` holds before the launch
+QPROJ_VARIANT_SHAPES = {32: (224, 28), 64: (448, 56)}  # padded head dim -> (input channels, real head dim)
+
+
+def attn_variant_name(family, d, qt):
+    return family + str(d) + ("q%d" % qt if (d <= 128) else "")
+
+
+def launch_geometry(nq, qt, wpb):
+    """(workgroups along the queries, valid rows of the last live wave, waves with no valid query) of nq queries in
+    waves of 16 qt rows, wpb waves per workgroup."""
+    rows = 16 * qt
+    live = -(-nq // rows)
+    wgs = -(-nq // (rows * wpb))
+    return wgs, nq - (live - 1) * rows, wgs * wpb - live
+
+
+def attn_variant_rows():
+    """The table: one dict per (variant, shape).  `wpbs`: the waves per workgroup the row is launched with (all give the
+    same bits); `w`: the one its n_q was sized for, and `claim` = (workgroups, valid rows of the last live wave, idle waves)
+    at that w, written out here and recomputed from launch_geometry by the host test."""
+    rows = []
+
+    def add(family, d, qt, nq, nkv, w, claim, causal=False, B=2, heads=3, **kw):
+        rows.append(dict(family=family, variant=attn_variant_name(family, d, qt), d=d, qt=qt, nq=nq, nkv=nkv, w=w, claim=claim,
+                         causal=causal, B=B, heads=heads, wpbs=ATTN_WPB[family], **kw))
+
+    # n_q = 16 qt w + 16 qt + 5: one workgroup more than the full ones; the last live wave holds 5 valid rows (with qt = 2
+    # its second group is wholly invalid); w = 1 makes that three workgroups of one wave, w = 2 two workgroups with every
+    # wave live, w = 4 two workgroups whose last two waves lie past the end
+    ragged = {1: (3, 5, 0), 2: (2, 5, 0), 4: (2, 5, 2)}
+    for d in (32, 64, 128):
+        for qt in (1, 2):
+            for w in (1, 2, 4):
+                # 1: a single key; 33: a 32-key tile, then a tail tile with one valid key; 64: exactly one 64-key tile;
+                # 95: a 64-key tile, then a masked tail; 160: two 64-key tiles, then a full 32-key tile
+                for nkv in (1, 33, 64, 95, 160):
+                    add("direct", d, qt, 16 * qt * w + 16 * qt + 5, nkv, w, ragged[w])
+    for d in (256, 512):
+        for w in (1, 2, 4):
+            for nkv in (1, 50, 96):
+                add("direct", d, 1, 16 * w + 21, nkv, w, ragged[w], heads=3 if d == 256 else 2)
+    # one head of 512 with a ragged key count: the fall-through from the wide path to attn_kernel<512,0,1>
+    add("direct", 512, 1, 16 * 4 + 21, 50, 4, ragged[4], heads=1)
+    # causal (n_q == n_kv == n): 1 key; 17: two waves at qt = 1; 77: CLIP's length; 150: the 64-key loop with the q0-limited
+    # end, then the 32-key form
+    causal_claim = {(1, 1): (1, 1, 3), (1, 2): (1, 1, 3), (17, 1): (1, 1, 2), (17, 2): (1, 17, 3), (77, 1): (2, 13, 3),
+                    (77, 2): (1, 13, 1), (150, 1): (3, 6, 2), (150, 2): (2, 22, 3)}
+    for d in (32, 64):
+        for qt in (1, 2):
+            for n in (1, 17, 77, 150):
+                add("direct", d, qt, n, n, 4, causal_claim[(n, qt)], causal=True)
+    for qt in (1, 2):
+        add("direct", 128, qt, 77, 77, 4, causal_claim[(77, qt)], causal=True)
+    # LDS-staged: four and five 64-key tiles (the last one in either buffer); 7 queries (one live wave of four), and
+    # 64 qt + 21: two workgroups, the second with 21 rows (qt = 1: 16 + 5 in two waves; qt = 2: one wave, 16 + 5 in its
+    # two groups) and waves with no valid query that still have to reach every barrier
+    lds_claim = {(7, 1): (1, 7, 3), (7, 2): (1, 7, 3), (85, 1): (2, 5, 2), (149, 2): (2, 21, 3)}
+    for d in (32, 64):
+        for qt in (1, 2):
+            for nkv in (256, 320):
+                for nq in (7, 64 * qt + 21):
+                    add("lds", d, qt, nq, nkv, 4, lds_claim[(nq, qt)])
+    # wide: one tile (nothing is prefetched), three and five tiles; 1, 70 (two workgroups, 6 rows in the second) and 128
+    # queries (two full workgroups); ldk = 512 is the dense layout, ldk = 1024 the production one
+    wide_claim = {1: (1, 1, 3), 70: (2, 6, 3), 128: (2, 16, 0)}
+    for nkv in (32, 96, 160):
+        for nq in (1, 70, 128):
+            add("wide", 512, 1, nq, nkv, 4, wide_claim[nq], B=3, heads=1)
+    # query projection inside: (input channels, padded head dim, real head dim) = (224, 32, 28) with two query groups per
+    # wave and (448, 64, 56) with one
+    for d, qt in ((32, 2), (64, 1)):
+        for w in (1, 2, 4):
+            for nkv in (1, 64, 87):
+                add("qproj", d, qt, 16 * qt * w + 16 * qt + 5, nkv, w, ragged[w])
+    return rows
+
+
+def attn_variant_case(row, s, device="cpu"):
+    """The operands of a table row at scale s: attn_case's dict, or qproj_case's for the qproj family."""
+    if row["family"] == "qproj":
+        C, dh = QPROJ_VARIANT_SHAPES[row["d"]]
+        return qproj_case(s, dict(C=C, heads=row["heads"], dh=dh, nq=row["nq"], nkv=row["nkv"]), B=row["B"])
+    name = "%s_%d_%d" % (row["variant"], row["nq"], row["nkv"])
+    return attn_case(name, s, (row["d"], row["nq"], row["nkv"], row["causal"]), B=row["B"], heads=row["heads"], device=device)
+
+
+def attn_layout(q, k, v, heads, d, nq, layout):
+    """Device (or host) buffers and leading dimensions for one launch.  q [B, nq, heads * d] or None (the qproj entry point
+    has no q), k, v [B, nkv, heads * d], fp16.
+      'dense':       q, k, out contiguous, vt_ld = round_up(nkv, 32).
+      'production':  q and k are the column halves of one [B * n, 2 heads d] buffer when nq == nkv (the self-attention of
+                     the engines), else column slices of two such buffers whose other half holds NaN; vt_ld =
+                     round_up(nkv, 32) + 32 with NaN in the columns at and beyond round_up(nkv, 32), which no kernel may
+                     read; out starts a [B, nq + 2, heads d + 8] buffer.
+    Both: vt holds zeros in [nkv, round_up(nkv, 32)); out holds ATTN_FILL.  -> dict with the tensors q, k, vt, out (their
+    data_ptr() is what the launch gets), the buffer out lives in, and ldq, qbs, ldk, kbs, vt_ld, ldo, obs."""
+    B, nkv, hd = k.shape
+    assert hd == heads * d and layout in ("dense", "production")
+    new = lambda shape, val: torch.full(shape, val, dtype=torch.float16, device=k.device)
+    nan, rup = float("nan"), (nkv + 31) // 32 * 32
+    L = dict(layout=layout, q=None, nq=nq, nkv=nkv, hd=hd)
+    if layout == "dense":
+        L.update(q=q.contiguous() if q is not None else None, k=k.contiguous(), ldq=hd, qbs=nq * hd, ldk=hd, kbs=nkv * hd,
+                 vt_ld=rup, ldo=hd, obs=nq * hd)
+        vt, L["out_buf"] = new((B, heads, d, rup), 0.0), new((B, nq, hd), ATTN_FILL)
+    else:
+        if q is not None and nq == nkv:
+            qb = kb = new((B * nq, 2 * hd), nan)
+        else:
+            qb, kb = (new((B * nq, 2 * hd), nan) if q is not None else None), new((B * nkv, 2 * hd), nan)
+        if q is not None:
+            qb[:, :hd] = q.reshape(B * nq, hd)
+            L["q"] = qb[:, :hd]
+        kb[:, hd:] = k.reshape(B * nkv, hd)
+        L.update(k=kb[:, hd:], ldq=2 * hd, qbs=nq * 2 * hd, ldk=2 * hd, kbs=nkv * 2 * hd, vt_ld=rup + 32, ldo=hd + 8,
+                 obs=(nq + 2) * (hd + 8))
+        vt, L["out_buf"] = new((B, heads, d, rup + 32), nan), new((B, nq + 2, hd + 8), ATTN_FILL)
+        vt[..., :rup] = 0
+    vt[..., :nkv] = v.reshape(B, nkv, heads, d).permute(0, 2, 3, 1)
+    L.update(vt=vt, out=L["out_buf"])
+    return L
+
+
+def attn_layout_decode(L, B, heads, d):
+    """(q or None, k, v) [B, n, heads * d] read back from a layout's buffers through its leading dimensions alone."""
+    hd, nq, nkv = heads * d, L["nq"], L["nkv"]
+    q = torch.as_strided(L["q"], (B, nq, hd), (L["qbs"], L["ldq"], 1)) if L["q"] is not None else None
+    k = torch.as_strided(L["k"], (B, nkv, hd), (L["kbs"], L["ldk"], 1))
+    v = torch.as_strided(L["vt"], (B, heads, d, nkv), (heads * d * L["vt_ld"], d * L["vt_ld"], L["vt_ld"], 1))
+    return q, k, v.permute(0, 3, 1, 2).reshape(B, nkv, hd)
+
+
+def attn_owned(L):
+    """The part of a layout's out buffer the launch owns: [B, nq, heads * d]."""
+    return L["out_buf"][:, :L["nq"], :L["hd"]]
+
+
+def attn_outside_untouched(L):
+    """True when every element of the out buffer outside [0, nq) x [0, heads d) still holds ATTN_FILL bit for bit."""
+    t = L["out_buf"].clone()
+    t[:, :L["nq"], :L["hd"]] = ATTN_FILL
+    return bool((t.view(torch.int16) == torch.tensor(ATTN_FILL, dtype=torch.float16).view(torch.int16).item()).all())
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -606,7 +606,10 @@ def test_qkv_gemm_with_transposed_v(ctx):
                                             (32, 100, 87, 2), (512, 200, 200, 1),
                                             # d >= 256 (VAE mid-block): 1 / 2 / 4 waves per workgroup by launch size
                                             (512, 1024, 1024, 1), (256, 600, 130, 16), (256, 1024, 96, 16),
-                                            # LDS-staged K/V tiles (nkv % 64 == 0, >= 256): QT=2 and QT=1, ragged nq
+                                            # LDS-staged K/V tiles (nkv % 64 == 0, >= 256), ragged nq.  All four run ONE
+                                            # query group per wave at B = 2 (two need ceil(nq / 128) * B * heads >= 4 CUs'
+                                            # worth: 512, 48, 32, 160 here against 1024); the two-group kernels are pinned
+                                            # in tests/test_attention_variants_gpu.py
                                             (32, 1024, 1024, 32), (32, 1000, 256, 3), (64, 256, 256, 8), (64, 200, 320, 40)])
 def test_attention(ctx, d, nq, nkv, heads):
     B = 2

@@ -27,6 +27,8 @@ SYMBOLS = [
     "upk_nchw_f32_to_nhwc_f16", "upk_nhwc_f16_to_nchw_f32", "upk_f32_to_f16", "upk_ddim_step_f32",
     "upk_ddim_step_cfg_f32", "upk_ddim_step_edit_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_dpmpp_2m_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
     "upk_attention_fewkeys_f16", "upk_gelu_f16",
+    "upk_attention_num_variants", "upk_attention_variant_name", "upk_attention_override", "upk_attention_plan",
+    "upk_attention_qproj_plan",
     "upk_patchify_nchw_f32_f16", "upk_vit_assemble_f16", "upk_gather_rows_f16",
     "upk_image_finish_u8", "upk_resize_bilinear_u8", "upk_segm_boxes_u8", "upk_style_crops_u8",
     "upk_cond_bbox_u8", "upk_cond_gather_u8", "upk_cond_smpl_u8", "upk_clip_normalize_u8", "upk_ssim_ws_bytes", "upk_ssim_u8",
@@ -173,6 +175,13 @@ def load_library(path=None):
                                                   i32, i64, i32, i32, i32, i32, i32, f32, vp]),
             "upk_attention_fewkeys_f16": (C.c_int, [vp, vp, i32, i64, vp, i32, i64, vp, i32, i64, vp, i32, i64,
                                                     i32, i32, i32, i32, i32, f32, vp]),
+            "upk_attention_num_variants": (C.c_int, []),
+            "upk_attention_variant_name": (C.c_char_p, [i32]),
+            "upk_attention_override": (C.c_int, [vp, i32, i32]),
+            "upk_attention_plan": (C.c_int, [vp, vp, i32, i64, vp, i32, i64, vp, i32, vp, i32, i64,
+                                             i32, i32, i32, i32, i32, f32, vp, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+            "upk_attention_qproj_plan": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                                                   C.POINTER(C.c_int), C.POINTER(C.c_int)]),
             "upk_gelu_f16": (C.c_int, [vp, vp, i32, i32, i32, vp]),
             "upk_embed_tokens_f16": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp]),
             "upk_gather_rows_f16": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, vp, i32, vp]),
@@ -327,6 +336,29 @@ class Context:
     def attention_causal(self, q, ldq, qbs, k, ldk, kbs, vt, vt_ld, out, ldo, obs, batch, heads, n, d, scale):
         self._chk(self.lib.upk_attention_causal_f16(self.h, _ptr(q), ldq, qbs, _ptr(k), ldk, kbs, _ptr(vt), vt_ld,
                                                     _ptr(out), ldo, obs, batch, heads, n, d, scale, self._s()))
+
+    def attention_variants(self):
+        """Names of the compiled attention instantiations, by index (upk_attention_variant_name)."""
+        return [self.lib.upk_attention_variant_name(i).decode() for i in range(self.lib.upk_attention_num_variants())]
+
+    def attention_override(self, variant=-1, wpb=0):
+        """Forces the attention variant / waves per workgroup of the next launches; the defaults restore the heuristic."""
+        self._chk(self.lib.upk_attention_override(self.h, variant, wpb))
+
+    def attention_plan(self, q, ldq, qbs, k, ldk, kbs, vt, vt_ld, out, ldo, obs, batch, heads, n_q, n_kv, d, scale,
+                       causal=False):
+        """-> (variant index, waves per workgroup) a launch with these arguments would run; enqueues nothing."""
+        v, w = C.c_int(-1), C.c_int(0)
+        self._chk(self.lib.upk_attention_plan(self.h, _ptr(q), ldq, qbs, _ptr(k), ldk, kbs, _ptr(vt), vt_ld, _ptr(out), ldo,
+                                              obs, batch, heads, n_q, n_kv, d, scale, self._s(), int(causal), C.byref(v),
+                                              C.byref(w)))
+        return v.value, w.value
+
+    def attention_qproj_plan(self, ldx, cq, ln_dim, ldk, vt_ld, ldo, batch, heads, n_q, n_kv, d):
+        v, w = C.c_int(-1), C.c_int(0)
+        self._chk(self.lib.upk_attention_qproj_plan(self.h, ldx, cq, ln_dim, ldk, vt_ld, ldo, batch, heads, n_q, n_kv, d,
+                                                    C.byref(v), C.byref(w)))
+        return v.value, w.value
 
     def attention_fewkeys(self, q, ldq, qbs, k, ldk, kbs, v, ldv, vbs, out, ldo, obs, batch, heads, n_q, n_kv, d, scale):
         """upk_attention_fewkeys_f16: 1 <= n_kv <= 16 keys, k / v in the natural [B, n_kv, ld] layout (column slices of one

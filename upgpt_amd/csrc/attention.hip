@@ -650,14 +650,117 @@ __global__ __launch_bounds__(256) void attn_wide_kernel(const AttnArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// The compiled instantiations (upk_attention_variant_name; indices are only ever appended) and the ONE procedure that
+// picks among them: the launchers and the queries (upk_attention_plan, upk_attention_qproj_plan) both call attn_decide.
+enum { AF_DIRECT = 0, AF_LDS = 1, AF_WIDE = 2, AF_QPROJ = 3 };
+struct AttnVariant {
+  const char* name;
+  int family, d, qt;
+};
+static const AttnVariant kAttnVariants[] = {
+    {"direct32q1", AF_DIRECT, 32, 1},  {"direct32q2", AF_DIRECT, 32, 2},   {"direct64q1", AF_DIRECT, 64, 1},
+    {"direct64q2", AF_DIRECT, 64, 2},  {"direct128q1", AF_DIRECT, 128, 1}, {"direct128q2", AF_DIRECT, 128, 2},
+    {"direct256", AF_DIRECT, 256, 1},  {"direct512", AF_DIRECT, 512, 1},   {"lds32q1", AF_LDS, 32, 1},
+    {"lds32q2", AF_LDS, 32, 2},        {"lds64q1", AF_LDS, 64, 1},         {"lds64q2", AF_LDS, 64, 2},
+    {"wide512", AF_WIDE, 512, 1},      {"qproj32q2", AF_QPROJ, 32, 2},     {"qproj64q1", AF_QPROJ, 64, 1},
+};
+constexpr int kNumAttnVariants = (int)(sizeof(kAttnVariants) / sizeof(kAttnVariants[0]));
+
+static int attn_variant_index(int family, int d, int qt) {
+  for (int i = 0; i < kNumAttnVariants; ++i)
+    if (kAttnVariants[i].family == family && kAttnVariants[i].d == d && kAttnVariants[i].qt == qt) return i;
+  return -1;
+}
+
+// What a launch with these arguments runs: the instantiation and its waves per workgroup.  Precedence: the context's
+// override (upk_attention_override), then the environment knobs (read once), then the heuristic.  An override never
+// bypasses a path's preconditions: a forced variant or waves-per-workgroup the arguments cannot take is refused
+// (UPK_ESHAPE), never approximated, and the caller launches nothing.  `qproj`: the upk_attention_qproj_f16 entry point
+// (q == nullptr, ldq == qbs == 0).  The caller has validated the arguments of its entry point.
+static int attn_decide(upk_ctx* ctx, bool qproj, const void* q, int ldq, long long qbs, const void* k, int ldk,
+                       long long kbs, const void* vt, int vt_ld, int batch, int heads, int n_q, int n_kv, int d,
+                       int causal, int* variant, int* wpb_out) {
+  if (d != 32 && d != 64 && d != 128 && d != 256 && d != 512)
+    return upk_fail(ctx, UPK_ESHAPE, "attention: head dim %d not in {32,64,128,256,512}", d);
+  // long self-attention sequences: K / V^T tiles shared through LDS (whole 64-key tiles only)
+  const bool lds_ok = !qproj && !causal && (d == 32 || d == 64) && n_kv >= 256 && (n_kv & 63) == 0 && (vt_ld & 7) == 0;
+  // the VAE mid-block attention on LDS-shared key tiles (attn_wide_kernel): one head, whole 32-key tiles, rows of K
+  // that are exactly one 1 KiB request; anything else takes the direct kernel
+  // (16-byte LDS-DMA pieces and f16x8 Q loads: every row / sample stride a multiple of 8 halves, 16-byte bases)
+  const bool wide_ok = !qproj && d == 512 && heads == 1 && !causal && (n_kv & 31) == 0 && ldk >= 512 &&
+                       ((ldk | ldq | vt_ld) & 7) == 0 && ((kbs | qbs) & 7) == 0 &&
+                       (((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt) & 15) == 0;
+  int family, qt;
+  const int forced = ctx->attn_variant_override;
+  if (forced >= 0) {
+    if (forced >= kNumAttnVariants) return upk_fail(ctx, UPK_ESHAPE, "attention: no variant %d", forced);
+    const AttnVariant& v = kAttnVariants[forced];
+    if ((v.family == AF_QPROJ) != qproj)
+      return upk_fail(ctx, UPK_ESHAPE, "attention: variant %s does not belong to this entry point", v.name);
+    if (v.d != d) return upk_fail(ctx, UPK_ESHAPE, "attention: variant %s forced at head dim %d", v.name, d);
+    if (v.family == AF_LDS && !lds_ok)
+      return upk_fail(ctx, UPK_ESHAPE, "attention: variant %s needs n_kv %% 64 == 0, n_kv >= 256, vt_ld %% 8 == 0, no mask", v.name);
+    if (v.family == AF_WIDE && !wide_ok)
+      return upk_fail(ctx, UPK_ESHAPE, "attention: variant %s needs one head, n_kv %% 32 == 0, ldk >= 512, strides %% 8 == 0, "
+                      "16-byte aligned q / k / vt, no mask", v.name);
+    family = v.family;
+    qt = v.qt;
+  } else if (qproj) {
+    family = AF_QPROJ;
+    qt = d == 32 ? 2 : 1;  // (d = 64: two query groups per wave measured slower: 21.5 vs 17.8 us at 256 x 8 heads)
+  } else {
+    // two 16-query groups per wave when there are enough queries to give every CU four workgroups even so (at two per CU —
+    // the 32x32 level at B = 8: 512 workgroups of 128 queries — the single-group form with its 1024 workgroups hides the
+    // K / V tile latency better: forward 2.890 -> 2.867 ms, -4.5 us per launch in situ, same-box A/B of UPK_ATTN_QT)
+    static const int qt_env = getenv("UPK_ATTN_QT") ? atoi(getenv("UPK_ATTN_QT")) : 0;  // dev
+    static const bool lds_off = getenv("UPK_ATTN_DIRECT") != nullptr;
+    static const bool wide_off = getenv("UPK_ATTN_WIDE_OFF") != nullptr;  // (read once: lane threads call this concurrently)
+    qt = qt_env ? (qt_env == 2 ? 2 : 1) : ((d <= 128 && (long)((n_q + 127) / 128) * batch * heads >= 4L * ctx->num_cus) ? 2 : 1);
+    if (d > 128) qt = 1;
+    family = (lds_ok && !lds_off) ? AF_LDS : (wide_ok && !wide_off) ? AF_WIDE : AF_DIRECT;
+  }
+  // the direct and qproj kernels keep no state between waves: fewer waves per workgroup while that gives more CUs work;
+  // the LDS-staged and wide kernels are written for four
+  const bool four = family == AF_LDS || family == AF_WIDE;
+  int wpb = four ? 4 : attn_waves_per_block(ctx, batch * heads, n_q, qt);
+  const int wf = ctx->attn_wpb_override;
+  if (wf > 0) {
+    if (wf != 1 && wf != 2 && wf != 4) return upk_fail(ctx, UPK_ESHAPE, "attention: %d waves per workgroup not in {1,2,4}", wf);
+    if (four && wf != 4)
+      return upk_fail(ctx, UPK_ESHAPE, "attention: the LDS-staged and wide kernels run four waves per workgroup, not %d", wf);
+    wpb = wf;
+  }
+  *variant = attn_variant_index(family, d, qt);
+  *wpb_out = wpb;
+  if (*variant < 0) return upk_fail(ctx, UPK_ESHAPE, "attention: no kernel for head dim %d with %d query groups per wave", d, qt);
+  return UPK_OK;
+}
+
+static int attn_validate(upk_ctx* ctx, const void* q, int ldq, const void* k, int ldk, const void* vt, int vt_ld,
+                         const void* out, int ldo, int batch, int heads, int n_q, int n_kv, int causal) {
+  if (!q || !k || !vt || !out) return upk_fail(ctx, UPK_EINVAL, "attention: null pointer");
+  if (batch <= 0 || heads <= 0 || n_q <= 0 || n_kv <= 0) return upk_fail(ctx, UPK_EINVAL, "attention: empty");
+  // (a forced wide512 names its own stride condition: it is the stricter one, and a forced variant the arguments cannot
+  // take is UPK_ESHAPE whichever check sees it first)
+  const int forced = ctx->attn_variant_override;
+  if (forced >= 0 && forced < kNumAttnVariants && kAttnVariants[forced].family == AF_WIDE && ((ldk | ldq | vt_ld) & 7))
+    return upk_fail(ctx, UPK_ESHAPE, "attention: variant %s needs ldq, ldk and vt_ld %% 8 == 0", kAttnVariants[forced].name);
+  if ((ldq & 7) || (ldk & 7) || (vt_ld & 3) || (ldo & 3) || vt_ld < ((n_kv + 31) & ~31))
+    return upk_fail(ctx, UPK_EINVAL, "attention: ldq/ldk %% 8, vt_ld %% 4 and vt_ld >= round_up(n_kv,32) required");
+  if (causal && n_q != n_kv) return upk_fail(ctx, UPK_EINVAL, "attention: causal needs n_q == n_kv");
+  return UPK_OK;
+}
+
 static int attention_impl(upk_ctx* ctx, const void* q, int ldq, long long qbs, const void* k, int ldk, long long kbs,
                           const void* vt, int vt_ld, void* out, int ldo, long long obs, int batch, int heads, int n_q,
                           int n_kv, int d, float scale, int causal, upk_stream stream_) {
   if (!ctx) return UPK_EINVAL;
-  if (!q || !k || !vt || !out) return upk_fail(ctx, UPK_EINVAL, "attention: null pointer");
-  if (batch <= 0 || heads <= 0 || n_q <= 0 || n_kv <= 0) return upk_fail(ctx, UPK_EINVAL, "attention: empty");
-  if ((ldq & 7) || (ldk & 7) || (vt_ld & 3) || (ldo & 3) || vt_ld < ((n_kv + 31) & ~31))
-    return upk_fail(ctx, UPK_EINVAL, "attention: ldq/ldk %% 8, vt_ld %% 4 and vt_ld >= round_up(n_kv,32) required");
+  int rc = attn_validate(ctx, q, ldq, k, ldk, vt, vt_ld, out, ldo, batch, heads, n_q, n_kv, causal);
+  if (rc != UPK_OK) return rc;
+  int variant = -1, wpb = 0;
+  rc = attn_decide(ctx, false, q, ldq, qbs, k, ldk, kbs, vt, vt_ld, batch, heads, n_q, n_kv, d, causal, &variant, &wpb);
+  if (rc != UPK_OK) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   AttnArgs a;
   a.q = (const f16*)q;
@@ -676,72 +779,43 @@ static int attention_impl(upk_ctx* ctx, const void* q, int ldq, long long qbs, c
   a.nkv = n_kv;
   a.scale_log2 = scale * 1.4426950408889634f;
   a.causal = causal;
-  if (causal && n_q != n_kv) return upk_fail(ctx, UPK_EINVAL, "attention: causal needs n_q == n_kv");
-  // two 16-query groups per wave when there are enough queries to give every CU four workgroups even so (at two per CU —
-  // the 32x32 level at B = 8: 512 workgroups of 128 queries — the single-group form with its 1024 workgroups hides the
-  // K / V tile latency better: forward 2.890 -> 2.867 ms, -4.5 us per launch in situ, same-box A/B of UPK_ATTN_QT)
-  static const int qt_env = getenv("UPK_ATTN_QT") ? atoi(getenv("UPK_ATTN_QT")) : 0;  // dev
-  const int qt = qt_env ? qt_env : ((d <= 128 && (long)((n_q + 127) / 128) * batch * heads >= 4L * ctx->num_cus) ? 2 : 1);
-  // grid.x = (sample, head): workgroups go to XCDs round-robin by linear index, so with batch * heads a multiple of 8
-  // every query block of a (sample, head) lands on the same XCD and K / V are fetched over the fabric once, not 8 times
-  dim3 grid(batch * heads, (n_q + 64 * qt - 1) / (64 * qt)), block(256);
+  const AttnVariant& v = kAttnVariants[variant];
   upk_prof_scope prof(ctx, UPK_CLS_ATTN, stream);
-  // long self-attention sequences: K / V^T tiles shared through LDS (whole 64-key tiles only)
-  static const bool lds_off = getenv("UPK_ATTN_DIRECT") != nullptr;
-  if (!lds_off && !causal && (d == 32 || d == 64) && n_kv >= 256 && (n_kv & 63) == 0 && (vt_ld & 7) == 0) {
-    if (d == 32) {
-      if (qt == 2) hipLaunchKernelGGL((attn_lds_kernel<32, 2>), grid, block, 0, stream, a);
+  if (v.family == AF_LDS) {
+    // grid.x = (sample, head): workgroups go to XCDs round-robin by linear index, so with batch * heads a multiple of 8
+    // every query block of a (sample, head) lands on the same XCD and K / V are fetched over the fabric once, not 8 times
+    const dim3 grid(batch * heads, (n_q + 64 * v.qt - 1) / (64 * v.qt)), block(256);
+    if (v.d == 32) {
+      if (v.qt == 2) hipLaunchKernelGGL((attn_lds_kernel<32, 2>), grid, block, 0, stream, a);
       else hipLaunchKernelGGL((attn_lds_kernel<32, 1>), grid, block, 0, stream, a);
     } else {
-      if (qt == 2) hipLaunchKernelGGL((attn_lds_kernel<64, 2>), grid, block, 0, stream, a);
+      if (v.qt == 2) hipLaunchKernelGGL((attn_lds_kernel<64, 2>), grid, block, 0, stream, a);
       else hipLaunchKernelGGL((attn_lds_kernel<64, 1>), grid, block, 0, stream, a);
     }
     return upk_check_launch(ctx, "attention_lds");
   }
-  // the kernels below keep no state between waves: fewer waves per workgroup while that gives more CUs work
-  {
-    const int wpb = attn_waves_per_block(ctx, batch * heads, n_q, d <= 128 ? qt : 1);
-    if (d <= 128) {
-      grid = dim3(batch * heads, (n_q + 16 * qt * wpb - 1) / (16 * qt * wpb));
-      block = dim3(64 * wpb);
-    }
+  if (v.family == AF_WIDE) {
+    static unsigned long long wide_mask = 0;  // (set under upk_lds_attr_once's mutex)
+    int rcw = upk_lds_attr_once(ctx, (const void*)attn_wide_kernel<512>, &wide_mask);
+    if (rcw != UPK_OK) return rcw;
+    const size_t lds = 2 * (32 * (512 * 2 + 32) + 512 * 64);
+    hipLaunchKernelGGL((attn_wide_kernel<512>), dim3(batch, (n_q + 63) / 64), dim3(256), lds, stream, a);
+    return upk_check_launch(ctx, "attention_wide");
   }
-#define UPK_ATTN(D_, QR_)                                                                         \
-  if (qt == 2)                                                                                    \
-    hipLaunchKernelGGL((attn_kernel<D_, QR_, (D_ <= 128 ? 2 : 1)>), grid, block, 0, stream, a);  \
-  else                                                                                            \
+  // the direct kernels (d = 512: every wave streams the whole K / V^T of its sample through the CU's vector-memory path,
+  // so fewer waves per workgroup until every CU has work; B = 8: 128 workgroups of 4 waves -> 512 of 1)
+  const dim3 grid(batch * heads, (n_q + 16 * v.qt * wpb - 1) / (16 * v.qt * wpb)), block(64 * wpb);
+#define UPK_ATTN(D_, QR_)                                                                        \
+  if (v.qt == 2)                                                                                 \
+    hipLaunchKernelGGL((attn_kernel<D_, QR_, (D_ <= 128 ? 2 : 1)>), grid, block, 0, stream, a); \
+  else                                                                                           \
     hipLaunchKernelGGL((attn_kernel<D_, QR_, 1>), grid, block, 0, stream, a);
-  switch (d) {
+  switch (v.d) {
     case 32: UPK_ATTN(32, 1) break;
     case 64: UPK_ATTN(64, 1) break;
     case 128: UPK_ATTN(128, 1) break;
-    case 512:
-      // the VAE mid-block attention on LDS-shared key tiles (attn_wide_kernel): one head, whole 32-key tiles, rows of K
-      // that are exactly one 1 KiB request; anything else falls through to the direct kernel below
-      // (16-byte LDS-DMA pieces and f16x8 Q loads: every row / sample stride a multiple of 8 halves, 16-byte bases)
-      static const bool wide_off = getenv("UPK_ATTN_WIDE_OFF") != nullptr;  // (read once: lane threads call this concurrently)
-      if (heads == 1 && !causal && (n_kv & 31) == 0 && ldk >= 512 && !wide_off &&
-          ((ldk | ldq | vt_ld) & 7) == 0 && ((kbs | qbs) & 7) == 0 &&
-          (((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt) & 15) == 0) {
-        static unsigned long long wide_mask = 0;  // (set under upk_lds_attr_once's mutex)
-        int rcw = upk_lds_attr_once(ctx, (const void*)attn_wide_kernel<512>, &wide_mask);
-        if (rcw != UPK_OK) return rcw;
-        const size_t lds = 2 * (32 * (512 * 2 + 32) + 512 * 64);
-        hipLaunchKernelGGL((attn_wide_kernel<512>), dim3(batch, (n_q + 63) / 64), dim3(256), lds, stream, a);
-        return upk_check_launch(ctx, "attention_wide");
-      }
-      [[fallthrough]];
-    case 256: {
-      // the VAE mid-block attention (one head, d = 512, 1024 tokens: model.py:180-196): every wave streams the whole K / V^T
-      // of its sample through the CU's vector-memory path, so fewer waves per workgroup until every CU has work
-      // (B = 8: 128 workgroups of 4 waves -> 512 of 1)
-      const int wpb = attn_waves_per_block(ctx, batch * heads, n_q, 1);
-      const dim3 g2(batch * heads, (n_q + 16 * wpb - 1) / (16 * wpb)), b2(64 * wpb);
-      if (d == 256) hipLaunchKernelGGL((attn_kernel<256, 1, 1>), g2, b2, 0, stream, a);
-      else hipLaunchKernelGGL((attn_kernel<512, 0, 1>), g2, b2, 0, stream, a);
-      break;
-    }
-    default: return upk_fail(ctx, UPK_ESHAPE, "attention: head dim %d not in {32,64,128,256,512}", d);
+    case 256: hipLaunchKernelGGL((attn_kernel<256, 1, 1>), grid, block, 0, stream, a); break;
+    default: hipLaunchKernelGGL((attn_kernel<512, 0, 1>), grid, block, 0, stream, a); break;
   }
 #undef UPK_ATTN
   return upk_check_launch(ctx, "attention");
@@ -760,6 +834,52 @@ extern "C" int upk_attention_causal_f16(upk_ctx* ctx, const void* q, int ldq, lo
   return attention_impl(ctx, q, ldq, qbs, k, ldk, kbs, vt, vt_ld, out, ldo, obs, batch, heads, n, n, d, scale, 1, stream);
 }
 
+extern "C" int upk_attention_num_variants(void) { return kNumAttnVariants; }
+
+extern "C" const char* upk_attention_variant_name(int variant) {
+  return (variant >= 0 && variant < kNumAttnVariants) ? kAttnVariants[variant].name : "?";
+}
+
+extern "C" int upk_attention_override(upk_ctx* ctx, int variant, int wpb) {
+  if (!ctx) return UPK_EINVAL;
+  ctx->attn_variant_override = variant < 0 ? -1 : variant;
+  ctx->attn_wpb_override = wpb <= 0 ? 0 : wpb;
+  return UPK_OK;
+}
+
+extern "C" int upk_attention_plan(upk_ctx* ctx, const void* q, int ldq, long long qbs, const void* k, int ldk,
+                                  long long kbs, const void* vt, int vt_ld, const void* out, int ldo, long long obs,
+                                  int batch, int heads, int n_q, int n_kv, int d, float scale, upk_stream stream,
+                                  int causal, int* variant, int* wpb) {
+  (void)obs;
+  (void)scale;
+  (void)stream;  // (the launch's argument list as it stands; nothing is enqueued)
+  if (!ctx) return UPK_EINVAL;
+  if (!variant || !wpb) return upk_fail(ctx, UPK_EINVAL, "attention_plan: null result pointer");
+  int rc = attn_validate(ctx, q, ldq, k, ldk, vt, vt_ld, out, ldo, batch, heads, n_q, n_kv, causal);
+  if (rc != UPK_OK) return rc;
+  return attn_decide(ctx, false, q, ldq, qbs, k, ldk, kbs, vt, vt_ld, batch, heads, n_q, n_kv, d, causal, variant, wpb);
+}
+
+static int qproj_validate(upk_ctx* ctx, int ldx, int cq, int ln_dim, int ldk, int vt_ld, int ldo, int batch, int heads,
+                          int n_q, int n_kv, int d) {
+  if (batch <= 0 || heads <= 0 || n_q <= 0 || n_kv <= 0) return upk_fail(ctx, UPK_EINVAL, "attention_qproj: empty");
+  if ((ldx & 7) || (ldk & 7) || (vt_ld & 3) || (ldo & 3) || vt_ld < ((n_kv + 31) & ~31))
+    return upk_fail(ctx, UPK_EINVAL, "attention_qproj: ldx/ldk %% 8, vt_ld %% 4 and vt_ld >= round_up(n_kv,32) required");
+  if ((d != 32 && d != 64) || cq <= 0 || cq % 224 || ln_dim <= 0 || ln_dim > cq || ldx < cq)
+    return upk_fail(ctx, UPK_ESHAPE, "attention_qproj: head dim %d / %d input channels outside {32,64} / 224*n", d, cq);
+  return UPK_OK;
+}
+
+extern "C" int upk_attention_qproj_plan(upk_ctx* ctx, int ldx, int cq, int ln_dim, int ldk, int vt_ld, int ldo, int batch,
+                                        int heads, int n_q, int n_kv, int d, int* variant, int* wpb) {
+  if (!ctx) return UPK_EINVAL;
+  if (!variant || !wpb) return upk_fail(ctx, UPK_EINVAL, "attention_qproj_plan: null result pointer");
+  int rc = qproj_validate(ctx, ldx, cq, ln_dim, ldk, vt_ld, ldo, batch, heads, n_q, n_kv, d);
+  if (rc != UPK_OK) return rc;
+  return attn_decide(ctx, true, nullptr, 0, 0, nullptr, ldk, 0, nullptr, vt_ld, batch, heads, n_q, n_kv, d, 0, variant, wpb);
+}
+
 extern "C" int upk_attention_qproj_f16(upk_ctx* ctx, const void* x, int ldx, long long xbs, int cq, int ln_dim,
                                        float ln_eps, const void* wq, const float* wq_colsum, const float* wq_bias,
                                        const void* k, int ldk, long long kbs, const void* vt, int vt_ld, void* out,
@@ -767,11 +887,11 @@ extern "C" int upk_attention_qproj_f16(upk_ctx* ctx, const void* x, int ldx, lon
                                        float scale, upk_stream stream_) {
   if (!ctx) return UPK_EINVAL;
   if (!x || !wq || !wq_colsum || !wq_bias || !k || !vt || !out) return upk_fail(ctx, UPK_EINVAL, "attention_qproj: null pointer");
-  if (batch <= 0 || heads <= 0 || n_q <= 0 || n_kv <= 0) return upk_fail(ctx, UPK_EINVAL, "attention_qproj: empty");
-  if ((ldx & 7) || (ldk & 7) || (vt_ld & 3) || (ldo & 3) || vt_ld < ((n_kv + 31) & ~31))
-    return upk_fail(ctx, UPK_EINVAL, "attention_qproj: ldx/ldk %% 8, vt_ld %% 4 and vt_ld >= round_up(n_kv,32) required");
-  if ((d != 32 && d != 64) || cq <= 0 || cq % 224 || ln_dim <= 0 || ln_dim > cq || ldx < cq)
-    return upk_fail(ctx, UPK_ESHAPE, "attention_qproj: head dim %d / %d input channels outside {32,64} / 224*n", d, cq);
+  int rc = qproj_validate(ctx, ldx, cq, ln_dim, ldk, vt_ld, ldo, batch, heads, n_q, n_kv, d);
+  if (rc != UPK_OK) return rc;
+  int variant = -1, wpb = 0;
+  rc = attn_decide(ctx, true, nullptr, 0, 0, k, ldk, kbs, vt, vt_ld, batch, heads, n_q, n_kv, d, 0, &variant, &wpb);
+  if (rc != UPK_OK) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   AttnArgs a;
   a.q = nullptr;
@@ -800,9 +920,8 @@ extern "C" int upk_attention_qproj_f16(upk_ctx* ctx, const void* x, int ldx, lon
   p.cq = cq;
   p.ln_dim = ln_dim;
   p.eps = ln_eps;
+  const int qt = kAttnVariants[variant].qt;
   upk_prof_scope prof(ctx, UPK_CLS_ATTN, stream);
-  const int qt = d == 32 ? 2 : 1;  // (d = 64: two query groups per wave measured slower: 21.5 vs 17.8 us at 256 x 8 heads)
-  const int wpb = attn_waves_per_block(ctx, batch * heads, n_q, qt);
   const dim3 grid((n_q + 16 * qt * wpb - 1) / (16 * qt * wpb), batch * heads), block(64 * wpb);
   if (d == 32) hipLaunchKernelGGL((attn_qproj_kernel<32, 2>), grid, block, 0, stream, a, p);
   else hipLaunchKernelGGL((attn_qproj_kernel<64, 1>), grid, block, 0, stream, a, p);

@@ -44,6 +44,8 @@ struct upk_ctx {
   void* zero_page;  // >= 256 B of zeros in HBM (padding source for direct-to-LDS loads)
   int cfg_override;
   int splitk_override;
+  int attn_variant_override;  // upk_attention_override: forced instantiation (-1: the heuristic) ...
+  int attn_wpb_override;      // ... and waves per workgroup (0: the heuristic)
   void* tune_flush;  // 512 MB cache-flush buffer of the cold autotuner (allocated on first use)
   int* step_done;    // upk_step_autoadvance: arrival counter of the sampler step kernels, or nullptr
   long long n_kernels;  // kernels enqueued through this context (upk_kernel_launches)

@@ -45,6 +45,8 @@ extern "C" int upk_create(upk_ctx** out, int device) {
   }
   c->cfg_override = -1;
   c->splitk_override = 0;
+  c->attn_variant_override = -1;
+  c->attn_wpb_override = 0;
   c->prof_on = 0;
   for (int i = 0; i < UPK_NUM_CLASSES; ++i) {
     c->prof_ms[i] = 0;

@@ -41,6 +41,9 @@ class Program:
         self.keep = []
         self.flops = []  # algorithmic FLOPs of each op (conv / GEMM launches; 0 elsewhere)
         self.meta = []   # ConvDesc of a upk_conv2d launch (its tuned configuration names the kernel instantiation), else None
+        # sizes, strides and scale (no pointers) of every emitted attention launch, in order: kind "attn" (upk_attention_f16)
+        # or "qproj" (upk_attention_qproj_f16); what tests/test_attention_variants_gpu.py replays variant by variant
+        self.attn = []
         self.igemm_flops = 0
         self.attn_flops = 0
         self.n_launch = 0
@@ -691,6 +694,8 @@ class Emitter:
         fn, h, chk = self.lib.upk_attention_f16, self.hctx, self._chk
         a = (q.data_ptr(), ldq, qbs, k.data_ptr(), ldk, kbs, vt.data_ptr(), vt_ld, out.data_ptr(), ldo, obs, B, heads,
              nq, nkv, dp, float(scale))
+        P.attn.append(dict(kind="attn", ldq=ldq, qbs=qbs, ldk=ldk, kbs=kbs, vt_ld=vt_ld, ldo=ldo, obs=obs, B=B, heads=heads,
+                           nq=nq, nkv=nkv, d=dp, scale=float(scale), align=(q.data_ptr() | k.data_ptr() | vt.data_ptr()) & 15))
         P.add(lambda s: chk(fn(h, *a, s)), q, k, vt, out, cls="attention",
               label="attn B%d h%d nq%d nkv%d d%d" % (B, heads, nq, nkv, dp))
 

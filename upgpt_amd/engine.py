@@ -165,6 +165,9 @@ class UNetPlan(Emitter):
             qa = (t1.t.data_ptr(), t1.ld, HW * t1.ld, t1.C, t1.C, 1e-5, wq.data_ptr(), wu.data_ptr(), wb.data_ptr(),
                   kc.t.data_ptr(), hd, self.n_ctx * hd, vtc.data_ptr(), cld, a2.t.data_ptr(), hd, HW * hd, B, heads, HW,
                   self.n_ctx, dp, float(scale))
+            P.attn.append(dict(kind="qproj", ldx=t1.ld, xbs=HW * t1.ld, cq=t1.C, ln_dim=t1.C, eps=1e-5, ldk=hd,
+                               kbs=self.n_ctx * hd, vt_ld=cld, ldo=hd, obs=HW * hd, B=B, heads=heads, nq=HW, nkv=self.n_ctx,
+                               d=dp, scale=float(scale)))
             P.add(lambda s: chk(fn(hh, *qa, s)), t1, wq, wu, wb, kc, vtc, a2, cls="attention",
                   label="attn+q B%d h%d nq%d nkv%d d%d C%d" % (B, heads, HW, self.n_ctx, dp, t1.C))
             P.igemm_flops += 2 * M * heads * dh * t1.C
