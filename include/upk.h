@@ -774,6 +774,65 @@ int upk_style_crops_u8(upk_ctx* ctx, const uint8_t* pictures, long long pic_pitc
                        upk_stream stream);
 
 /* ------------------------------------------------------------------ */
+/* Region-locked editing: label map -> edit mask, pixel-space composite. */
+/* ------------------------------------------------------------------ */
+/* The two per-pixel passes around a masked sampling chain: which pixels may change, as a picture-
+ * resolution mask and as the latent-resolution keep-mask the samplers take, and the blend of the generated picture into
+ * the original ON THE BYTES, so that everything outside the feathered region is the input, byte for byte.  Integers
+ * only: no result depends on an order of evaluation.
+ *   strides   in bytes, any value with pitch >= the bytes of a row, no alignment; sample strides are ignored for
+ *             batch == 1
+ *
+ * upk_region_mask_u8
+ *   segm      uint8 label maps, label of pixel (y, x) of sample b at segm[b * segm_sample_stride + y * segm_pitch + x]
+ *   label_sel_host   HOST uint32 [8], a 256-bit set read during the call and handed to the kernel by value: bit l % 32 of
+ *             word l / 32 is set when label l is selected
+ *   sel(y, x) = 1 when the label of the pixel is selected.  M(y, x) = 1 when some sel(y', x') = 1 with |y - y'| <= dilate
+ *             and |x - x'| <= dilate (a Chebyshev window; pixels outside the picture count as unselected).
+ *   mask_u8   may be NULL: byte (y, x) of sample b at mask_u8[b * mask_sample_stride + y * mask_pitch + x] = 255 where M,
+ *             else 0.  Bytes of a row beyond w are not touched.
+ *   keep      may be NULL: DEVICE fp32 dense [batch, 1, h / factor, w / factor]: exactly 0.0f when any pixel of the cell's
+ *             factor x factor block has M = 1, else exactly 1.0f (the samplers' convention: 1 keeps x0)
+ *   cells     may be NULL: DEVICE int32 [batch], the number of cells with keep = 0.  WRITTEN, not accumulated: the caller
+ *             does not zero it.  (Counted by one extra workgroup per sample from the bit rows of the whole map; it exists
+ *             only when cells is given.)
+ * Errors (UPK_EINVAL): null segm or label_sel_host, no output at all, non-positive sizes, dilate outside 0 .. 32, factor not
+ * one of 1, 2, 4, 8, 16, h % factor or w % factor not 0, segm_pitch < w, mask_pitch < w (with a mask), keep or cells not
+ * 4-byte aligned, overlapping mask samples (a sample stride below one sample's extent), a mask that overlaps the label
+ * maps.
+ *
+ * upk_composite_u8
+ *   orig, gen   uint8 pictures, byte (c) of pixel (y, x) of sample b at p[b * ss + y * pitch + 3 x + c]
+ *   mask_u8     uint8 [h][w] per sample (pitch, ss): m(y, x) = (byte != 0)
+ *   n = (2 feather + 1)^2;  s(y, x) = the sum of m over the (2 feather + 1)^2 window with CLAMPED coordinates (edge
+ *             replication);  A = (255 s + n / 2) / n, integer division, 0 .. 255
+ *   out       out_c = (A gen_c + (255 - A) orig_c + 127) / 255, integer division, per channel: A = 0 gives the original
+ *             byte exactly, A = 255 the generated byte exactly.  Layout as orig / gen.
+ *   alpha_out may be NULL: uint8 [h][w] per sample (alpha_pitch, alpha_ss), receives A
+ * Errors (UPK_EINVAL): null orig, gen, mask_u8 or out, non-positive sizes, feather outside 0 .. 16, a picture pitch below
+ * 3 w, a mask / alpha pitch below w, out or alpha_out overlapping an input or each other, overlapping output samples.
+ * orig, gen, out (and alpha_out) with 4-byte aligned pointers, pitches and sample strides take dword loads and stores
+ * (12 bytes = 4 pixels); everything else, and the last w % 4 pixels of a row, go per pixel with the same results.
+ *
+ * Both work on bit rows: a wave turns 64 adjacent bytes of a row into one 64-bit word in LDS with one ballot (a label map
+ * or mask whose width, address, pitch and sample stride are multiples of 16 is read by 16-byte loads instead, a lane ORs
+ * its 16 bits into the word; same results), a window is then a few word operations (OR for the dilation, popcount for
+ * the box sum).  A workgroup owns a band of 16 rows of one
+ * picture: the bit rows its window covers, a barrier, the vertical pass, the band's bytes and cells (16 is a multiple of
+ * every factor: a cell never straddles two workgroups).  UPK_ESHAPE: a size whose bit rows do not fit 64 KiB of LDS
+ * (region_mask: (48 + 2 dilate) ceil(w / 64) 8 bytes, and with cells (h + h / factor) ceil(w / 64) 8 bytes; composite:
+ * (16 + 2 feather) (ceil(w / 64) 8 + w rounded up to 4) bytes), or batch > 65535; never approximated.  Every picture up
+ * to 512 x 384 fits at dilate 32 / feather 16.  Nothing is launched on an error.  One launch each, class "other".  Never
+ * allocate, never synchronise, graph-capturable. */
+int upk_region_mask_u8(upk_ctx* ctx, const uint8_t* segm, long long segm_pitch, long long segm_sample_stride, int batch,
+                       int h, int w, const uint32_t* label_sel_host, int dilate, int factor, uint8_t* mask_u8,
+                       long long mask_pitch, long long mask_sample_stride, float* keep, int32_t* cells, upk_stream stream);
+int upk_composite_u8(upk_ctx* ctx, const uint8_t* orig, long long orig_pitch, long long orig_ss, const uint8_t* gen,
+                     long long gen_pitch, long long gen_ss, const uint8_t* mask_u8, long long mask_pitch, long long mask_ss,
+                     int batch, int h, int w, int feather, uint8_t* out, long long out_pitch, long long out_ss,
+                     uint8_t* alpha_out, long long alpha_pitch, long long alpha_ss, upk_stream stream);
+
+/* ------------------------------------------------------------------ */
 /* The test split's loader: conditioning maps and stored style crops.    */
 /* ------------------------------------------------------------------ */
 /* The per-pixel work of DeepFashionPair.__getitem__ (deepfashion_inshop.py:173-272) on the bytes PIL decoded.  Every

@@ -31,6 +31,7 @@ SYMBOLS = [
     "upk_attention_qproj_plan",
     "upk_patchify_nchw_f32_f16", "upk_vit_assemble_f16", "upk_gather_rows_f16",
     "upk_image_finish_u8", "upk_resize_bilinear_u8", "upk_segm_boxes_u8", "upk_style_crops_u8",
+    "upk_region_mask_u8", "upk_composite_u8",
     "upk_cond_bbox_u8", "upk_cond_gather_u8", "upk_cond_smpl_u8", "upk_clip_normalize_u8", "upk_ssim_ws_bytes", "upk_ssim_u8",
     "upk_pose_interp_f32",
     "upk_lpips_input_f16", "upk_relu_pool_nhwc_f16", "upk_lpips_ws_bytes", "upk_lpips_layer_f16",
@@ -216,6 +217,10 @@ def load_library(path=None):
             "upk_style_crops_u8": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, i32, i32, i32, C.POINTER(C.c_uint32), i32, vp,
                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, C.POINTER(C.c_float), vp, vp, vp,
                                              vp, vp]),
+            "upk_region_mask_u8": (C.c_int, [vp, vp, i64, i64, i32, i32, i32, C.POINTER(C.c_uint32), i32, i32, vp, i64, i64, vp,
+                                             vp, vp]),
+            "upk_composite_u8": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, vp, i64, i64, vp,
+                                           i64, i64, vp]),
             "upk_cond_bbox_u8": (C.c_int, [vp, vp, i64, i64, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp]),
             "upk_cond_gather_u8": (C.c_int, [vp, vp, i64, i64, i32, i32, i32, vp, vp, i32, i32, C.POINTER(C.c_float), vp, vp]),
             "upk_cond_smpl_u8": (C.c_int, [vp, vp, i64, i64, i32, i32, i32, vp, vp]),
@@ -480,6 +485,26 @@ class Context:
                                               int(segm_ss), int(batch), int(h), int(w), lg, int(n_groups), _ptr(boxes), gf, sl,
                                               0 if slot_groups is None else len(slot_groups), ms, _ptr(dst_u8), _ptr(dst_f32),
                                               _ptr(valid), _ptr(coeff_out), self._s()))
+
+    def region_mask(self, segm, segm_pitch, segm_ss, batch, h, w, labels, dilate, factor, mask_u8=None, mask_pitch=0,
+                    mask_ss=0, keep=None, cells=None):
+        """upk_region_mask_u8; labels: the selected label ids (host integers 0 .. 255), or None for a null set."""
+        sel = None
+        if labels is not None:
+            sel = (C.c_uint32 * 8)()
+            for l in labels:
+                sel[int(l) >> 5] |= 1 << (int(l) & 31)
+        self._chk(self.lib.upk_region_mask_u8(self.h, _ptr(segm), int(segm_pitch), int(segm_ss), int(batch), int(h), int(w), sel,
+                                              int(dilate), int(factor), _ptr(mask_u8), int(mask_pitch), int(mask_ss), _ptr(keep),
+                                              _ptr(cells), self._s()))
+
+    def composite(self, orig, orig_pitch, orig_ss, gen, gen_pitch, gen_ss, mask_u8, mask_pitch, mask_ss, batch, h, w, feather,
+                  out, out_pitch, out_ss, alpha_out=None, alpha_pitch=0, alpha_ss=0):
+        """upk_composite_u8: out <- gen blended into orig under the box-feathered mask; alpha_out (may be None) <- A."""
+        self._chk(self.lib.upk_composite_u8(self.h, _ptr(orig), int(orig_pitch), int(orig_ss), _ptr(gen), int(gen_pitch),
+                                            int(gen_ss), _ptr(mask_u8), int(mask_pitch), int(mask_ss), int(batch), int(h), int(w),
+                                            int(feather), _ptr(out), int(out_pitch), int(out_ss), _ptr(alpha_out),
+                                            int(alpha_pitch), int(alpha_ss), self._s()))
 
     def cond_bbox(self, src, pitch, ss, batch, h, w, ytab, xtab, out_h, out_w, dst, boxes):
         """upk_cond_bbox_u8: the box of every map's non-zero bytes -> boxes int32 [batch, 4] and the NEAREST-resized box map."""

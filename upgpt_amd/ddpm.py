@@ -733,6 +733,31 @@ class LatentDiffusion(AncestralSampling, DDPM):
         return log
 
     @torch.no_grad()
+    def edit_images(self, batch, keep, N=8, ddim_steps=200, ddim_eta=1., noise_keys=None, **kwargs):
+        """Region-locked editing (this package's extension): the batch's pictures are encoded and sampled
+        again under the latent keep-mask `keep` [>= n, 1, *image_size] (1 keeps x0, 0 is generated: edit.region_mask's
+        second result), with the batch's conditioning -> {'reconstruction', 'samples'} like log_images.  get_input as
+        log_images calls it, then the masked chain of sample_log(x0=z, mask=keep) under the EMA scope, then the decoder;
+        `kwargs` carry sampler=, the guidance arguments and so on, as in log_images.  noise_keys: draw 4 (fork(4); draws
+        0 to 3 belong to log_images), the posterior sample behind z is keyed as there.  The decoded picture differs from
+        the input OUTSIDE the region as well (the VAE round trip, and the last step's result is never blended): the
+        byte-exact guarantee is edit.composite's, in pixel space."""
+        z, cond, x, xrec, _ = self.get_input(batch, self.first_stage_key, return_first_stage_outputs=True,
+                                             force_c_encode=True, return_original_cond=True, bs=N,
+                                             **({} if noise_keys is None else {"noise_keys": noise_keys}))
+        n = min(x.shape[0], N)
+        require(z is not None, "region editing needs the first stage's encoder", NotImplementedError)
+        require(torch.is_tensor(keep) and keep.dim() == 4 and keep.shape[0] >= n and keep.shape[1] == 1 and
+                tuple(keep.shape[2:]) == tuple(self.image_size),
+                lambda: "keep must be [>= %d, 1, %d, %d], got %s" % (n, self.image_size[0], self.image_size[1], tuple(
+                    keep.shape) if torch.is_tensor(keep) else type(keep).__name__), ValueError)
+        keyed = {} if noise_keys is None else {"noise_keys": noise_keys[:n].fork(4)}
+        with self.ema_scope("Plotting Edit"):
+            samples, _ = self.sample_log(cond=cond, batch_size=n, ddim=ddim_steps is not None, ddim_steps=ddim_steps,
+                                         eta=ddim_eta, x0=z[:n], mask=keep[:n].to(self.device, torch.float32), **keyed, **kwargs)
+        return {"reconstruction": xrec, "samples": self.decode_first_stage(samples.to(self.device))}
+
+    @torch.no_grad()
     def test_step(self, batch, batch_idx, **log_kwargs):
         """ddpm.py:1327-1377 — what trainer.test runs per batch (main.py:798): sample the batch through log_images and
         write results/{samples,concats,styles,gt,recon,src,smpl}/<fname>.jpg under self.logger.save_dir (a Lightning

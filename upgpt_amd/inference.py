@@ -287,6 +287,76 @@ class InferenceModel:
             return v[None] if isinstance(v, np.ndarray) or torch.is_tensor(v) else v
         return styles.style_crops(as_map(picture, "RGB"), as_map(segm, None), segmenter, style_names)[0][0]
 
+    def edit_region(self, picture, segm, region, batch, steps=200, use_ema=True, sampler="ddim", segmenter='lip', dilate=8,
+                    feather=4, noise_keys=None):
+        """Region-locked editing: the photo with ONE region generated anew, e.g. a new top, and every
+        pixel farther than dilate + feather from the old region byte-identical to the input.
+        picture: uint8 [H, W, 3] or [B, H, W, 3] (a PIL image, a host array or a tensor; a device tensor is read in
+        place), H x W the size the first stage decodes the model's latent to (ValueError otherwise); segm: the
+        human-parsing label map(s) uint8 [H, W] / [B, H, W]; region / segmenter: edit.region_labels ('top', 'bottom',
+        'hair', 'label:top', a list of names, ...).  batch: the conditioning as generate takes it after create_batch
+        (txt, styles, smpl, person_mask, ...), with the NEW style already in its slot (a crop or a text through
+        mix_style); it is not modified and an 'image' entry in it is ignored: the picture is the image.
+        On the device: the picture as the model's input (prepare.lr_transform with both passes skipped, the reference's
+        image_transform), edit.region_mask at the first stage's factor, LatentDiffusion.edit_images with generate's
+        guidance arguments, upk_image_finish_u8 for the generated bytes, edit.composite against the original bytes; one
+        copy and one synchronise at the end.  Returns host arrays {'edited' uint8 [B, H, W, 3], 'samples' uint8 [B, H,
+        W, 3] (the whole generated pictures), 'mask' uint8 [B, H, W], 'alpha' uint8 [B, H, W], 'cells' int32 [B]}.
+        A sample whose region is empty (cells 0) has alpha 0 everywhere and comes back as its input, with no special
+        case.  At most 8 samples per call, like generate: more is a ValueError, not a silent cut."""
+        from . import _lib, edit, prepare
+        from ._check import require
+        from .evaluate import finish_images
+
+        def as_array(v, mode):
+            if hasattr(v, "convert"):  # a PIL image
+                v = np.asarray(v.convert(mode) if mode == "RGB" else v, dtype=np.uint8)
+            return v
+        edit.region_labels(region, segmenter)  # (everything refusable is refused before anything is uploaded)
+        require(0 <= int(dilate) <= edit.MAX_DILATE, lambda: "dilate must be 0 .. %d, got %r" % (edit.MAX_DILATE, dilate), ValueError)
+        require(0 <= int(feather) <= edit.MAX_FEATHER, lambda: "feather must be 0 .. %d, got %r" % (edit.MAX_FEATHER, feather),
+                ValueError)
+        picture, segm = as_array(picture, "RGB"), as_array(segm, None)
+        if (isinstance(picture, np.ndarray) or torch.is_tensor(picture)) and picture.ndim == 3:
+            picture = picture[None]
+        if (isinstance(segm, np.ndarray) or torch.is_tensor(segm)) and segm.ndim == 2:
+            segm = segm[None]
+        picture, segm = edit._u8("picture", picture, "[H, W, 3] or [B, H, W, 3]", 4), edit._u8("segm", segm, "[H, W] or [B, H, W]", 3)
+        b, h, w = (int(v) for v in picture.shape[:3])
+        require(picture.shape[3] == 3, lambda: "3-channel pictures only, got %s" % (tuple(picture.shape),), ValueError)
+        require(tuple(segm.shape) == (b, h, w), lambda: "segm %s does not match picture %s" % (tuple(segm.shape), tuple(picture.shape)),
+                ValueError)
+        f = 2 ** int(self.model.num_downs)
+        size = [f * int(v) for v in self.model.image_size]
+        require([h, w] == size, lambda: "edit_region: a %d x %d picture, the model works on %d x %d" % (h, w, size[0], size[1]),
+                ValueError)
+        require(b <= InferenceModel.FRAMES_PER_CALL, lambda: "edit_region: %d samples, at most %d per call" % (
+            b, InferenceModel.FRAMES_PER_CALL), ValueError)
+        picture, segm = edit._on_device([picture, segm], "a region is edited on the MI355X (upk_region_mask_u8, upk_composite_u8)")
+        cond = {k: v for k, v in batch.items() if k != "image"}
+        cond["image"] = prepare.lr_transform(picture, size)[1]
+        mask, keep, cells = edit.region_mask(segm, region, segmenter, dilate, f)
+        extra = {} if sampler == "ddim" else {"sampler": sampler}
+        with torch.no_grad():
+            log = self.model.edit_images(cond, keep, N=b, ddim_steps=steps, noise_keys=noise_keys, use_ema=use_ema,
+                                         unconditional_guidance_scale=3., unconditional_guidance_label=[""], **extra)
+        samples = log["samples"].to(picture.device, torch.float32)
+        gen = torch.empty((b, h, w, 3), dtype=torch.uint8, device=picture.device)
+        finish_images(samples, gen, _lib.LAYOUT_NCHW, _lib.FINISH_SAMPLE)
+        edited, alpha = edit.composite(picture, gen, mask, feather, return_alpha=True)
+        parts = [("cells", cells, np.int32), ("edited", edited, np.uint8), ("samples", gen, np.uint8), ("mask", mask, np.uint8),
+                 ("alpha", alpha, np.uint8)]
+        buf = torch.cat([t.contiguous().view(torch.uint8).reshape(-1) for _, t, _ in parts])
+        host = torch.empty(buf.numel(), dtype=torch.uint8, pin_memory=True)
+        host.copy_(buf, non_blocking=True)
+        torch.cuda.current_stream(buf.device).synchronize()
+        arr, out, off = host.numpy(), {}, 0
+        for name, t, dtype in parts:
+            nbytes = t.numel() * t.element_size()
+            out[name] = arr[off:off + nbytes].view(dtype).reshape(tuple(t.shape)).copy()
+            off += nbytes
+        return out
+
     def mix_style(self, s, w, mask=[]):
         """Style embeddings [9, 768] of the crops `s` [9, 3, 224, 224]; slots named in `mask` are blanked (in `s`
         itself, as the reference does) and slots with a text in `w` take the CLIP TEXT embedding instead (:173-189)."""
