@@ -417,7 +417,7 @@ int upk_attention_qproj_f16(upk_ctx* ctx, const void* x, int ldx, long long xbs,
  *
  * upk_attention_override forces the variant and / or the waves per workgroup of the next launches of this context
  * (tests and tuning): variant < 0 and wpb <= 0 restore the heuristic (variant 0 is a variant).  Precedence: the override,
- * then the UPK_ATTN_* environment knobs, then the heuristic.  An override never bypasses what a kernel needs: the lds
+ * then the heuristic.  An override never bypasses what a kernel needs: the lds
  * variants need n_kv % 64 == 0, n_kv >= 256, vt_ld % 8 == 0 and no causal mask; wide512 needs one head, n_kv % 32 == 0,
  * ldk >= 512, ldq / ldk / vt_ld / batch strides % 8 == 0, 16-byte aligned q / k / vt and no causal mask; a variant runs
  * only at its own head dim and through its own entry point; wpb is 1, 2 or 4, and 4 for the lds and wide variants.

@@ -10,4 +10,3 @@ for ab in 0 0x10000 0x20000 0x80000 0xF0000; do
   echo "--- UPK_ABLATE=$ab (10000 noepi, 20000 noBload, 40000 noLDSread, 80000 nomfma)"
   UPK_ABLATE=$ab python scripts/ws_bench.py ff1_M8192 2>&1 | grep "cold "
 done
-for sk in 0 1 2 4 8; do echo "--- skew $sk"; UPK_AS_SKEW=$sk python scripts/ws_bench.py ff1_M8192 2>&1 | grep "cold "; done

@@ -135,6 +135,25 @@ def test_library_exports_every_declared_symbol():
     assert ctypes.sizeof(_lib.ConvDesc) % 8 == 0
 
 
+def test_library_reads_only_the_documented_environment():
+    """The launch choice is a function of the arguments, the context overrides and the tuning table: a default build of
+    libupk.so reads UPK_TUNE_COLD (upk_conv_autotune) and nothing else; the dev instrument's reads sit directly under a
+    conditional that only dev builds (-DUPK_DEV / -DUPK_TIMELINE) compile."""
+    reads = {}
+    csrc = os.path.join(ROOT, "upgpt_amd", "csrc")
+    for fn in sorted(os.listdir(csrc)):
+        guard = ""
+        for line in open(os.path.join(csrc, fn)):
+            if re.match(r"\s*#\s*(if|ifdef|ifndef|elif|else|endif)\b", line):
+                guard = line.strip()
+            for name in re.findall(r'getenv\("(\w+)"\)', line):
+                reads.setdefault(name, []).append((fn, guard))
+    assert set(reads) == {"UPK_TUNE_COLD", "UPK_ABLATE", "UPK_TL_TARGET", "UPK_MLP_TL", "UPK_XB_TL"}
+    for name in set(reads) - {"UPK_TUNE_COLD"}:
+        for fn, guard in reads[name]:
+            assert re.match(r"#\s*(if|ifdef)\b.*\b(UPK_DEV_HOOKS|UPK_TIMELINE)\b", guard), (name, fn, guard)
+
+
 def test_no_cpu_fallback():
     """Without a GPU the product path fails loudly (never routes through the oracle / torch CPU ops)."""
     m = upgpt_amd.build_model("tiny")

@@ -252,8 +252,8 @@ def test_unet_forward_with_and_without_the_fused_head():
 def test_head_block_behind_a_split_k_producer():
     """which GroupNorm path a fused SpatialTransformer head takes is decided by the TUNED configuration of
     the conv in front of it (upk_conv_gn_fused: 2 = channel partials of an unsplit launch -> normalisation inside the head;
-    1 = group partials of a split-K reduce -> apply launch + plain head; 3 = the reduce pass normalises itself, reachable
-    at the 32x32 level only with the dev knob UPK_GNAPPLY_NVMAX raised).  A tuning change could flip the path silently, so
+    1 = group partials of a split-K reduce -> apply launch + plain head; 3 = the reduce pass normalises itself, which the
+    32x32 level does not take).  A tuning change could flip the path silently, so
     this test forces the other one: every producer of a head's input is pinned to split-K = 2, and the forward must agree
     with the separate-GroupNorm reference path (HBLOCK_GN off)."""
     import ctypes as C

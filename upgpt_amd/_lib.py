@@ -731,7 +731,6 @@ def _unregister_pool(pool):
 
 
 _HOST_IO_LOCK = threading.RLock()
-_HOST_IO_OFF = os.environ.get("UPGPT_HOST_IO_LOCK", "1") == "0"  # (dev: A/B of the lock's cost)
 
 
 @contextlib.contextmanager
@@ -742,7 +741,7 @@ def host_io():
     mode), so the two never overlap.  The lane's own stream is drained BEFORE the lock is taken — a blocking upload waits
     for the stream's earlier work (the lane's previous batch, hundreds of ms in flight) and must not do that inside the
     lock.  A no-op with one batch in flight: the serial path is unchanged."""
-    if (concurrency() <= 1 and pools_in_flight() <= 1) or _HOST_IO_OFF:
+    if concurrency() <= 1 and pools_in_flight() <= 1:
         yield
         return
     if torch.cuda.is_available():

@@ -13,8 +13,6 @@
 // V arrives transposed ([B, heads, d, vt_ld]) straight from the projection GEMM's epilogue
 // (igemm.hip, vt_* fields), K/Q are token-major with heads side by side.  K/V fragments are
 // read through L1/L2 (per (b, head) they are <= 200 KB and shared by all query tiles).
-#include <stdlib.h>
-
 #include "common.h"
 
 namespace {
@@ -178,14 +176,9 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
   const int wave = threadIdx.x >> 6;
   const int g = lane >> 4, c = lane & 15;
   const int bh = blockIdx.x;  // (all query blocks of one (sample, head) on one XCD: its K / V cross the fabric once)
-#ifndef UPK_NO_XCD_SAMPLE
   const int nb_ = gridDim.x / a.heads;
   const int b = bh % nb_;
   const int h = bh / nb_;
-#else
-  const int b = bh / a.heads;
-  const int h = bh - b * a.heads;
-#endif
   const int q0 = (blockIdx.y * (blockDim.x >> 6) + wave) * 16 * QT;  // (1, 2 or 4 waves per workgroup: no wave talks to another)
   if (q0 >= a.nq) return;
   const f16* kbase = a.k + b * a.kbs + h * D + g * 8;
@@ -391,14 +384,9 @@ __global__ __launch_bounds__(256) void attn_lds_kernel(const AttnArgs a) {
   const int lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, c = lane & 15;
   const int bh = blockIdx.x;  // (see attn_kernel)
-#ifndef UPK_NO_XCD_SAMPLE
   const int nb_ = gridDim.x / a.heads;
   const int b = bh % nb_;
   const int h = bh / nb_;
-#else
-  const int b = bh / a.heads;
-  const int h = bh - b * a.heads;
-#endif
   const int q0 = (blockIdx.y * 4 + wave) * 16 * QT;
   const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
 
@@ -524,10 +512,7 @@ __global__ __launch_bounds__(256) void attn_lds_kernel(const AttnArgs a) {
 // launch has fewer than two workgroups per CU.  The UNet's 8x8 / 4x4-level launches are 64 (sample, head) pairs x 1-4
 // query groups: as 64 workgroups of 4 waves they load K / V through 64 CUs' vector-memory paths, as 256 of one wave
 // through all of them (forward 3.000 -> 2.966 ms; the VAE's d = 512 mid-block attention 0.40 -> 0.28 ms).
-// UPK_ATTN_WPB=n forces n (dev A/B).
 static int attn_waves_per_block(const upk_ctx* ctx, int bh, int n_q, int qt) {
-  static const int wpb_env = getenv("UPK_ATTN_WPB") ? atoi(getenv("UPK_ATTN_WPB")) : 0;
-  if (wpb_env == 1 || wpb_env == 2 || wpb_env == 4) return wpb_env;
   int wpb = 4;
   while (wpb > 1 && (long)bh * ((n_q + 16 * qt * wpb - 1) / (16 * qt * wpb)) < 2L * ctx->num_cus) wpb >>= 1;
   return wpb;
@@ -674,7 +659,7 @@ static int attn_variant_index(int family, int d, int qt) {
 }
 
 // What a launch with these arguments runs: the instantiation and its waves per workgroup.  Precedence: the context's
-// override (upk_attention_override), then the environment knobs (read once), then the heuristic.  An override never
+// override (upk_attention_override), then the heuristic — a pure function of the arguments.  An override never
 // bypasses a path's preconditions: a forced variant or waves-per-workgroup the arguments cannot take is refused
 // (UPK_ESHAPE), never approximated, and the caller launches nothing.  `qproj`: the upk_attention_qproj_f16 entry point
 // (q == nullptr, ldq == qbs == 0).  The caller has validated the arguments of its entry point.
@@ -712,13 +697,9 @@ static int attn_decide(upk_ctx* ctx, bool qproj, const void* q, int ldq, long lo
   } else {
     // two 16-query groups per wave when there are enough queries to give every CU four workgroups even so (at two per CU —
     // the 32x32 level at B = 8: 512 workgroups of 128 queries — the single-group form with its 1024 workgroups hides the
-    // K / V tile latency better: forward 2.890 -> 2.867 ms, -4.5 us per launch in situ, same-box A/B of UPK_ATTN_QT)
-    static const int qt_env = getenv("UPK_ATTN_QT") ? atoi(getenv("UPK_ATTN_QT")) : 0;  // dev
-    static const bool lds_off = getenv("UPK_ATTN_DIRECT") != nullptr;
-    static const bool wide_off = getenv("UPK_ATTN_WIDE_OFF") != nullptr;  // (read once: lane threads call this concurrently)
-    qt = qt_env ? (qt_env == 2 ? 2 : 1) : ((d <= 128 && (long)((n_q + 127) / 128) * batch * heads >= 4L * ctx->num_cus) ? 2 : 1);
-    if (d > 128) qt = 1;
-    family = (lds_ok && !lds_off) ? AF_LDS : (wide_ok && !wide_off) ? AF_WIDE : AF_DIRECT;
+    // K / V tile latency better: forward 2.890 -> 2.867 ms, -4.5 us per launch in situ, same-box A/B)
+    qt = (d <= 128 && (long)((n_q + 127) / 128) * batch * heads >= 4L * ctx->num_cus) ? 2 : 1;
+    family = lds_ok ? AF_LDS : wide_ok ? AF_WIDE : AF_DIRECT;
   }
   // the direct and qproj kernels keep no state between waves: fewer waves per workgroup while that gives more CUs work;
   // the LDS-staged and wide kernels are written for four

@@ -400,17 +400,8 @@ const BtCfg kBt[] = {
     BTC(8, 4, 2, 4, 4, true),  // 256x256 (wave 128x64)
     BTC(4, 8, 8, 1, 4, true),  // 512x128, 160 KB ring (N = 128 layers)
     BTC(4, 4, 4, 2, 4, true),  // 256x128,  96 KB ring (wave 64x64)
-#ifdef UPK_R6_EXPERIMENTS
-    // the 7 * 32-channel family of the UNet (N = 224, 448, 896, 1792): tiles of 224 / 112 columns without padding waste
-    // (round 6, generation 1 of VERDICT r05 item 1).  Two resident workgroups per CU: 67.6 / 70.7 KB rings,
-    // 4 waves, <= 256 registers; and the 8-wave 256x224 tile with half the weight bytes per output.  Parity-green
-    // (tests/test_bigtile_gpu.py runs every listed configuration), and slower by chip time on every UNet shape
-    // (profiles/r06_gen1_bigtile_224_columns_chip_time.txt: 12.3-15.2 us against 9.5 on the level-0 3x3 conv): with
-    // 64-workgroup launches on four lanes there is ONE workgroup per CU, and this family needs its sibling.  Dev builds only.
-    BTCF(4, 7, 2, 2, 3, false),  // 128x224 (wave 64x112)
-    BTCF(4, 7, 4, 1, 3, false),  // 256x112 (wave 64x112: A rows private, B shared)
-    BTC(4, 7, 4, 2, 4, true),    // 256x224, 120 KB ring (wave 64x112)
-#endif
+    // (224 / 112-column tiles for the UNet's 7 * 32-channel family were tried and were slower by chip time on every UNet
+    // shape, DESIGN.md 14b: with 64-workgroup launches on four lanes there is one workgroup per CU; not kept)
 };
 constexpr int kNumBt = sizeof(kBt) / sizeof(kBt[0]);
 
@@ -429,7 +420,7 @@ void bt_tile(int c, int* bm, int* bn, int* occ, int* mi, int* ni, int* wn) {
   *ni = kBt[c].ni;
 }
 int bt_launch(upk_ctx* ctx, const IgemmArgs& a, int c, dim3 grid, hipStream_t stream) {
-  // (split launches write fp32 slabs: no epilogue in the kernel)
+  // (split launches write partial slabs: no epilogue in the kernel)
   const bool fe = !a.partial && !Epi::plain(a);
   if (fe && !kBt[c].fn_fe) return upk_fail(ctx, UPK_ESHAPE, "conv: %s has no general-epilogue instantiation", kBt[c].name);
   hipLaunchKernelGGL(fe ? kBt[c].fn_fe : kBt[c].fn, grid, dim3(kBt[c].wm * kBt[c].wn * 64), 0, stream, a);

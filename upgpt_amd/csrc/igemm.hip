@@ -277,11 +277,8 @@ __device__ __forceinline__ void wait_vmcnt() {
 // LNF: the MFMA waves also take the folded LayerNorm's row statistics (IgemmArgs::ln_u) — likewise its own
 // instantiation (M x N split configurations only): a wave-uniform test per K chunk and 2*MI live registers less in
 // the kernels every other launch uses.
-// LW: loader waves (4, or 8 in the "...l8" configurations of round 6: the loaders' DMA ISSUE — each global_load_lds holds its
-// wave 60-185 cycles — is what bounds the K loop's fill at ~29 B/clk per CU; twice the issuers on the same ring.  Loader
-// waves 4 .. LW-1 take no part in the shared epilogue and leave after the K loop.)
-template <int MI, int NI, int WM, int WN, int KS, int NBUF, bool APP = false, bool LNF = false, int LW = 4>
-__global__ __launch_bounds__(256 + LW * 64) void igemm_ws_kernel(const IgemmArgs a) {
+template <int MI, int NI, int WM, int WN, int KS, int NBUF, bool APP = false, bool LNF = false>
+__global__ __launch_bounds__(512) void igemm_ws_kernel(const IgemmArgs a) {
   // WM*WN == 4: the 4 MFMA waves tile the block in M x N (each a MI x NI register tile).
   // WM*WN == 1: K-SPLIT mode — every MFMA wave owns the WHOLE MI x NI block tile and takes every
   // 4th K-chunk; the four accumulators are summed through LDS once at the end (fixed order).
@@ -294,7 +291,7 @@ __global__ __launch_bounds__(256 + LW * 64) void igemm_ws_kernel(const IgemmArgs
   constexpr int BM = MI * 16 * WM;
   constexpr int BN = NI * 16 * WN;
   constexpr int AG = BM / 16, BG = BN / 16;          // 16-row groups (1 KiB = one wave DMA)
-  static_assert(LW == 4 || (LW == 8 && !KSPLIT), "loader waves");
+  constexpr int LW = 4;                               // loader waves
   constexpr int AGW = (AG + LW - 1) / LW, BGW = (BG + LW - 1) / LW;  // groups per loader wave
   constexpr int P = KS * (AGW + BGW);                 // DMAs per loader wave per stage
   constexpr int D = NBUF - 1;                         // prefetch distance in stages
@@ -311,11 +308,7 @@ __global__ __launch_bounds__(256 + LW * 64) void igemm_ws_kernel(const IgemmArgs
   // already lets every wave finish any fragment)
   constexpr int NJ0 = (NI + 1) / 2, NJ1 = NI - NJ0;
   constexpr int HAND_OFF = 8192;  // bytes: behind tile_plain_cp's scratch (WM * WN * NI * 32 floats <= 4 KiB)
-#ifdef UPK_KSPLIT_EPI4
-  constexpr bool SHARE = false;
-#else
   constexpr bool SHARE = !KSPLIT && NJ1 >= 1 && HAND_OFF + 4 * MI * NJ1 * 1024 <= (NBUF * STAGE + DUMP) * 2;
-#endif
   static_assert(WM * WN * NI * 32 * 4 <= HAND_OFF, "tile_plain_cp scratch");
 
   if ABL_ON(ABL_EMPTY) return;
@@ -498,12 +491,6 @@ __global__ __launch_bounds__(256 + LW * 64) void igemm_ws_kernel(const IgemmArgs
     // K-split configurations: the loader waves stay for the epilogue — the four K slices meet in LDS anyway, and eight
     // waves finishing NF / 8 fragments each (operand round trip, stores, GroupNorm partials) are through in about half
     // the time four take (in-kernel stamps: epilogue 10-13 k of a 44 k-cycle launch)
-#ifdef UPK_KSPLIT_EPI4  // (A/B builds: the four MFMA waves alone)
-    return;
-#else
-    if constexpr (LW > 4) {
-      if (lw >= 4) return;  // (a finished wave no longer counts at the workgroup's barriers)
-    }
     if constexpr (!KSPLIT) {
       if constexpr (SHARE) {
         if ABL_ON(ABL_NOEPI) return;
@@ -524,39 +511,10 @@ __global__ __launch_bounds__(256 + LW * 64) void igemm_ws_kernel(const IgemmArgs
       }
       return;
     }
-#endif
   }
 
   // ================================ consumers ================================
   if (wave == 0) STAMP(0);
-#ifdef UPK_R6_EXPERIMENTS
-  if (a.pf_self) {
-    // (experiment, DESIGN.md 14h: dev builds only — it loses with four forwards in flight and on the latency table) this launch's OWN weight slice -> this XCD's L2, cooperatively: the workgroups of an XCD that
-    // share the (N tile, K split) slice each touch every cnt-th chunk of it up front, so that the slice is requested from HBM
-    // through cnt CUs' load windows at once instead of through each CU's own ~64 KB window, chunk after chunk
-    int rank, cnt;
-    if (a.xm_pm == 0) {  // default tile order: workgroup w = tile index runs on XCD w % 8, M tiles fastest
-      cnt = max(1, a.tiles_m >> 3);
-      rank = (tm >> 3) % cnt;
-    } else {
-      cnt = max(1, a.xm_mi);
-      rank = (int)(blockIdx.x >> 3) % cnt;
-    }
-    const int lpc = BN / 2;  // 128-byte lines of one chunk's BN x 64 B block
-    const int mine = (kc1 - kc0 - rank + cnt - 1) / cnt;  // chunks kc0 + rank, + cnt, ...
-    const int total = mine * lpc;
-    const int lines_ok = min(BN, a.npad - n0) / 2;  // (rows past n_pad do not exist)
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    typedef const __attribute__((address_space(1))) void* glb_ptr;
-    const f16* wb = a.w + (long)ph * a.ph_wstride + ((long)kc0 * a.npad + n0) * 32;
-    for (int l0 = wave * 64; l0 < total; l0 += 256) {
-      const int l = min(l0 + lane, total - 1);
-      const int ci = l / lpc, li = min(l - ci * lpc, lines_ok - 1);
-      const f16* src = wb + ((long)(rank + ci * cnt) * a.npad) * 32 + li * 64;
-      __builtin_amdgcn_global_load_lds((glb_ptr)src, (lds_ptr)(smem + NBUF * STAGE), 16, 0, 0);
-    }
-  }
-#endif
   if (a.pf_lines > 0) {
     // next launch's weights -> memory-side cache (include/upk.h pf_next): this workgroup's share of the lines, one 16-byte
     // piece per line and lane, by direct-to-LDS loads into the dump row group.  The MFMA waves have nothing to do until ring
@@ -654,11 +612,7 @@ __global__ __launch_bounds__(256 + LW * 64) void igemm_ws_kernel(const IgemmArgs
         for (int j = 0; j < NI; ++j) *(f32x4*)(red + ((wave * NF + i * NI + j) * 64 + lane) * 4) = acc[i][j];
     }
     __syncthreads();  // (all eight waves: the loaders come here from their last stage)
-#ifdef UPK_KSPLIT_EPI4
-    constexpr int EW = 4;
-#else
     constexpr int EW = 8;  // waves in the epilogue
-#endif
     if ABL_ON(ABL_NOEPI) return;
     auto frag_sum = [&](int f) {
       f32x4 v = *(const f32x4*)(red + ((0 * NF + f) * 64 + lane) * 4);
@@ -952,11 +906,7 @@ struct VecIO {
     }
   }
   static __device__ __forceinline__ void lds(const slab_t* p, bool on, float (&o)[V]) {  // (a split-K slab element)
-#ifdef UPK_SLAB_F32
-    ldf(p, on, o);
-#else
     ldh(p, on, o);
-#endif
   }
   static __device__ __forceinline__ void ldh(const f16* p, bool on, float (&o)[V]) {
     if constexpr (V == 4) {
@@ -1173,7 +1123,6 @@ struct CfgInfo {
   int nbuf;  // 0: classic register-staged kernel; > 0: wave-specialised DMA kernel (512 threads)
   void (*fn_app)(const IgemmArgs);  // variant whose loader walks an appended 1x1 K segment, or nullptr
   void (*fn_ln)(const IgemmArgs);   // variant whose MFMA waves take the folded LayerNorm's row statistics, or nullptr
-  int lw = 4;                       // loader waves of the wave-specialised kernel (threads = 256 + 64 lw)
 };
 
 template <int MI, int NI, int WM, int WN, int KS, int NB>
@@ -1186,11 +1135,7 @@ constexpr void (*ws_ln_fn())(const IgemmArgs) {
   {MI, NI, WM, WN, KS, #MI "x" #NI "x" #WM "x" #WN "k" #KS, igemm_kernel<MI, NI, WM, WN, KS>, 0, nullptr, nullptr}
 #define CFGW(MI, NI, WM, WN, KS, NB) \
   {MI, NI, WM, WN, KS, #MI "x" #NI "x" #WM "x" #WN "k" #KS "w" #NB, igemm_ws_kernel<MI, NI, WM, WN, KS, NB>, NB, \
-   igemm_ws_kernel<MI, NI, WM, WN, KS, NB, true>, ws_ln_fn<MI, NI, WM, WN, KS, NB>(), 4}
-// eight loader waves (768 threads); plain and appended-segment loaders, no fragment-side LayerNorm fold
-#define CFGW8(MI, NI, WM, WN, KS, NB) \
-  {MI, NI, WM, WN, KS, #MI "x" #NI "x" #WM "x" #WN "k" #KS "w" #NB "l8", igemm_ws_kernel<MI, NI, WM, WN, KS, NB, false, false, 8>, NB, \
-   igemm_ws_kernel<MI, NI, WM, WN, KS, NB, true, false, 8>, nullptr, 8}
+   igemm_ws_kernel<MI, NI, WM, WN, KS, NB, true>, ws_ln_fn<MI, NI, WM, WN, KS, NB>()}
 // (MI, NI, WM, WN, KS): block tile = (MI*16*WM) x (NI*16*WN), WM*WN waves, KS K-chunks/stage.
 const CfgInfo kCfgs[] = {
     CFG(4, 4, 2, 2, 1), CFG(4, 4, 2, 2, 2),  // 128x128
@@ -1221,14 +1166,6 @@ const CfgInfo kCfgs[] = {
     // 64-512 output rows; with 2 stages in flight each workgroup pays one HBM round trip per ~32 KB
     CFGW(2, 4, 2, 2, 2, 6), CFGW(4, 4, 2, 2, 1, 6), CFGW(2, 2, 2, 2, 2, 8), CFGW(2, 7, 4, 1, 1, 6),
     CFGW(1, 4, 4, 1, 2, 8), CFGW(4, 2, 2, 2, 2, 6),
-#ifdef UPK_R6_EXPERIMENTS
-    // round 6, generation 2 of VERDICT r05 item 1: the 128x224 / 128x128 tiles of the shared-chip table with
-    // (a) one-chunk stages on a 6-slot ring (112 KB in flight instead of 90, a barrier per chunk), (b) eight loader waves.
-    // Measured by chip time (profiles/r06_gen2_eight_loader_waves_deep_ring_chip_time.txt): 9.72 / 9.90 against 9.67 us on
-    // the level-0 3x3 conv — neither the ring depth nor the number of DMA issuers bounds the K loop.  Dev builds only
-    // (UPK_CXXFLAGS=-DUPK_R6_EXPERIMENTS): a configuration that does not win does not ship.
-    CFGW(4, 7, 2, 2, 1, 6), CFGW8(4, 7, 2, 2, 2, 3), CFGW8(4, 7, 2, 2, 1, 6), CFGW8(4, 4, 2, 2, 2, 3), CFGW8(2, 7, 2, 2, 2, 3),
-#endif
     // (256x128 / 128x256 tiles — 85 FLOP per filled byte against 64 — were tried for the VAE decoder's long convs:
     // 128 accumulator registers + the plain / statistics epilogues spill 50-200 VGPRs at 2 waves per SIMD; not kept)
 };
@@ -1355,8 +1292,7 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
   a.stride = d->stride;
   a.ph_on = 0;
   a.ph_wstride = 0;
-  static const bool ph_off = getenv("UPK_NO_PHASES") != nullptr;
-  const bool phases = d->w_phase && a.ups && d->ksize == 3 && d->stride == 1 && !(flags & UPK_F_PAD_ASYM) && !ph_off &&
+  const bool phases = d->w_phase && a.ups && d->ksize == 3 && d->stride == 1 && !(flags & UPK_F_PAD_ASYM) &&
                       !d->x3 && !d->ln_colsum && !d->vt && !d->residual && !d->rowvec &&
                       !(flags & (UPK_F_GEGLU | UPK_F_OUT_NCHW_F32));
   const int pad = (d->ksize == 3) ? 1 : 0;
@@ -1423,7 +1359,9 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
     a.nchunks += (a.c3 + a.c4) / 32;
   }
   a.flags = flags;
+#if UPK_DEV_HOOKS
   if (const char* ab = getenv("UPK_ABLATE")) a.flags |= (int)strtol(ab, nullptr, 0) & 0xFFF0000;
+#endif
   a.dbg = (unsigned long long*)((char*)ctx->ws + ctx->ws_bytes - 4096);
 
   // ---- choose config + split-K ----
@@ -1510,36 +1448,22 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
   a.tiles_n = is_as ? aspl.tiles_n : cdiv(a.npad, BN);
   a.chunks_per_split = cdiv(a.nchunks, best_sk);
   const int zdim = cdiv(a.nchunks, a.chunks_per_split);
-#ifdef UPK_R6_EXPERIMENTS
-  {
-    // (dev experiment) cooperative up-front touch of the launch's own weight slices: 0 off, 1 every wave-specialised
-    // launch, 2 only where a slice is shared by few M tiles and is large (the 16x16 and deeper levels), 3 = 2 with lanes only
-    static const int self_pf = getenv("UPK_SELF_PREFETCH") ? atoi(getenv("UPK_SELF_PREFETCH")) : 0;
-    static const int self_tm = getenv("UPK_SELF_PREFETCH_TM") ? atoi(getenv("UPK_SELF_PREFETCH_TM")) : 32;
-    const long slice = (long)BN * 64 * a.chunks_per_split;
-    a.pf_self = self_pf == 1 || (self_pf >= 2 && a.tiles_m <= self_tm && slice >= (256 << 10));
-  }
-#endif
   a.partial = (zdim > 1) ? (float*)ctx->ws : nullptr;
   // GroupNorm partials from the reduce pass (see igemm_reduce_gn_kernel)
   // ... or the whole GroupNorm from the reduce pass (igemm_reduce_gnapply_kernel)
-  int ga_v = 0, ga_nv = 0;
+  bool gn_apply = false;
+  int ga_nv = 0;
   if (d->gno_y && !a.ph_on && zdim > 1 && Epi::plain(a) && d->gn_groups > 0 && a.n_out % d->gn_groups == 0 && d->gno_gamma &&
       d->gno_beta) {
     const int cpg = a.n_out / d->gn_groups;
     // one workgroup per (sample, group) pays while a thread holds <= 2 vectors of 4 channels (the 4x4 / 8x8 levels:
     // 5.7 / 8.5 us against 6 + 6.5 us for reduce + GroupNorm launch); measured at 16x16 (2-wide vectors, 7 per thread)
     // 14 us and at 32x32 (scalars, 28 per thread) 36 us — those keep the statistics by-product + apply launch
-    const int v = !(cpg & 3) && !(a.ldy & 3) && !(d->gno_ld & 3) && (!a.res || !(a.ldr & 3)) ? 4 : (!(cpg & 1) ? 2 : 1);
-    const long nvec = (long)a.Ho * a.Wo * (cpg / v);
+    const bool v4 = !(cpg & 3) && !(a.ldy & 3) && !(d->gno_ld & 3) && (!a.res || !(a.ldr & 3));
+    const long nvec = (long)a.Ho * a.Wo * (cpg / 4);
     const int nv = (int)((nvec + 255) / 256);
-    static const int nv_max = getenv("UPK_GNAPPLY_NVMAX") ? atoi(getenv("UPK_GNAPPLY_NVMAX")) : 2;
-    // (never more vectors per thread than the widest instantiation below covers: <4, 8>, <2, 8>, <1, 32>)
-    const int nv_inst = v == 1 ? 32 : 8;
-    const int nv_lim = v == 4 ? (nv_max < nv_inst ? nv_max : nv_inst) : (nv_max > 2 ? nv_inst : 0);
-    if (nv <= nv_lim) ga_v = v, ga_nv = nv;
+    if (v4 && nv <= 2) gn_apply = true, ga_nv = nv;  // (the instantiations below: <4, 1>, <4, 2>)
   }
-  const bool gn_apply = ga_v != 0;
   const bool gn_fuse = !gn_apply && !a.ph_on && d->gn_stats_ws && zdim > 1 && Epi::plain(a) && !(a.n_out & 7) && a.n_out <= 2048 &&
                        d->gn_groups > 0 && d->gn_groups <= UPK_GN_GROUPS_MAX && a.n_out % d->gn_groups == 0 &&
                        !(a.ldy & 7) && (!a.res || !(a.ldr & 7));
@@ -1589,16 +1513,15 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
   // 3.5-7x the algorithmic bytes on the 16x16 ... 4x4 levels (scripts/pmc_fetch.sh)
   a.xm_pm = 0;
   a.xm_z = zdim;
-  static const int xmap = getenv("UPK_XCD_MAP") ? atoi(getenv("UPK_XCD_MAP")) : 2;  // 0 off, 1 without the 3x3 halo term, 2 default
   dim3 grid(a.tiles_m * a.tiles_n, nph, zdim);
-  if (xmap) {
+  {
     const long units = (long)a.tiles_n * zdim;
     const double Ab = (double)a.B * a.HS * a.WS * (a.c1 + a.c2) * 2.0 + (double)a.M * (a.c3 + a.c4) * 2.0;
     const double Wb = (double)a.nchunks * 32.0 * a.npad * 2.0;
     auto gcd = [](int x, int y) { while (y) { const int t = x % y; x = y; y = t; } return x; };
     // 3x3 convs: an M tile of r image rows also reads 2 halo rows; scattered over the XCDs every tile fetches its halo
     // itself ((r + 2) / r of the activations), a contiguous run of mi tiles per XCD shares all but its two outer rows
-    const bool halo = xmap > 1 && a.ks == 3 && a.stride == 1 && !a.ups && !a.ph_on && BM >= a.Wo;
+    const bool halo = a.ks == 3 && a.stride == 1 && !a.ups && !a.ph_on && BM >= a.Wo;
     const double rows = halo ? (double)BM / a.Wo : 1.0;
     const double h_def = halo ? (rows + 2.0) / rows : 1.0;
     const double cur = Wb * (a.tiles_m < 8 ? a.tiles_m : 8) +
@@ -1611,8 +1534,7 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
       const int mi = cdiv(a.tiles_m, pm), nj = (int)((units + pn - 1) / pn);
       // idle slots = one XCD with less work: harmless while every workgroup has a CU to itself (the grid is smaller
       // than the chip), a longer critical path otherwise (untuned 32x24 forward: +3 % with 20 % slots idle) -> exact fit
-      static const double slack_env = getenv("UPK_XCD_SLACK") ? atof(getenv("UPK_XCD_SLACK")) : 0.0;
-      const double slack = slack_env > 0.0 ? slack_env : ((long)8 * mi * nj * nph <= ctx->num_cus ? 1.2 : 1.0);
+      const double slack = (long)8 * mi * nj * nph <= ctx->num_cus ? 1.2 : 1.0;
       if ((double)8 * mi * nj > slack * (double)a.tiles_m * units) continue;
       const double c = Wb * pm + Ab * pn * (halo ? (rows * mi + 2.0) / (rows * mi) : 1.0);
       if (c < best) {
@@ -1629,7 +1551,7 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
   int rc;
   if (is_bt) rc = bt_launch(ctx, a, best - bt0, grid, stream);
   else {
-  hipLaunchKernelGGL((a.ln_u && !a.lnr_in) ? c.fn_ln : (a.x3 ? c.fn_app : c.fn), grid, dim3(c.nbuf ? 256 + 64 * c.lw : c.wm * c.wn * 64), 0, stream, a);
+  hipLaunchKernelGGL((a.ln_u && !a.lnr_in) ? c.fn_ln : (a.x3 ? c.fn_app : c.fn), grid, dim3(c.nbuf ? 512 : c.wm * c.wn * 64), 0, stream, a);
   rc = upk_check_launch(ctx, "igemm");
   }
   if (rc) return rc;
@@ -1645,16 +1567,10 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
     g.cpg = a.n_out / d->gn_groups;
     g.hw = a.Ho * a.Wo;
     const dim3 gg(d->gn_groups, a.B);
-    if (ga_v == 4 && ga_nv <= 1)
+    if (ga_nv <= 1)
       hipLaunchKernelGGL((igemm_reduce_gnapply_kernel<4, 1>), gg, dim3(256), 0, stream, a, zdim, g);
-    else if (ga_v == 4 && ga_nv <= 2)
-      hipLaunchKernelGGL((igemm_reduce_gnapply_kernel<4, 2>), gg, dim3(256), 0, stream, a, zdim, g);
-    else if (ga_v == 4)
-      hipLaunchKernelGGL((igemm_reduce_gnapply_kernel<4, 8>), gg, dim3(256), 0, stream, a, zdim, g);
-    else if (ga_v == 2)
-      hipLaunchKernelGGL((igemm_reduce_gnapply_kernel<2, 8>), gg, dim3(256), 0, stream, a, zdim, g);
     else
-      hipLaunchKernelGGL((igemm_reduce_gnapply_kernel<1, 32>), gg, dim3(256), 0, stream, a, zdim, g);
+      hipLaunchKernelGGL((igemm_reduce_gnapply_kernel<4, 2>), gg, dim3(256), 0, stream, a, zdim, g);
     rc = upk_check_launch(ctx, "igemm_reduce_gnapply");
   } else if (zdim > 1 && gn_fuse) {
     GnFuse gf;

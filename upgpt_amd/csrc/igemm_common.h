@@ -6,7 +6,7 @@
 
 namespace upkd {
 
-// debug-only ablation bits (env UPK_ABLATE, read per launch): which phase owns the time?
+// debug-only ablation bits (env UPK_ABLATE, read per launch in dev builds): which phase owns the time?
 enum {
   ABL_NOEPI = 0x10000,
   ABL_NOGLOAD = 0x20000,
@@ -17,13 +17,19 @@ enum {
   ABL_NOSTORE = 0x400000,   // plain epilogue: everything but the global stores of the output
   ABL_NOGNP = 0x800000,     // plain epilogue: no GroupNorm channel partials (column sums, LDS exchange, their stores)
   ABL_NOEPILD = 0x1000000,  // plain epilogue: operands (bias, row vector, residual) read as zeros, no loads
-  ABL_NOSLAB = 0x2000000,   // split-K launches: the partial slabs (fp16, fp32 with -DUPK_SLAB_F32) are not written
+  ABL_NOSLAB = 0x2000000,   // split-K launches: the partial slabs (fp16) are not written
   ABL_NOA = 0x4000000,      // WS loaders: every A (im2col) row group fetches the zero page — the requests stay, their lines do not
   ABL_NOB = 0x8000000,      // WS loaders: every B (weight) row group fetches the zero page
 };
 // The ablation / timeline hooks are compiled in only for dev builds (UPK_CXXFLAGS=-DUPK_DEV, scripts/ablate.sh,
 // scripts/timeline*.py): even as never-taken runtime tests they cost scalar registers and instructions in the loops.
+// UPK_DEV_HOOKS also guards every host-side read of a dev environment variable: a default build reads none of them.
 #if defined(UPK_DEV) || defined(UPK_TIMELINE)
+#define UPK_DEV_HOOKS 1
+#else
+#define UPK_DEV_HOOKS 0
+#endif
+#if UPK_DEV_HOOKS
 #define ABL_ON(f) ((a.flags & (f)) != 0)
 #else
 #define ABL_ON(f) (false)
@@ -47,7 +53,7 @@ struct IgemmArgs {
   int ldy;
   f16* vt;
   int vt_from, vt_heads, vt_dhead, vt_ld, vt_tokens;
-  float* partial;  // split-K slabs [splitk][M][npad] of slab_t (fp16 unless -DUPK_SLAB_F32; typed float* for the ABI's workspace), or nullptr
+  float* partial;  // split-K slabs [splitk][M][npad] of slab_t (fp16; typed float* for the ABI's workspace), or nullptr
   int M, n_out;
   int B, HS, WS;   // stored input dims
   int HL, WL;      // logical input dims (after optional 2x upsample)
@@ -95,33 +101,23 @@ struct IgemmArgs {
   // ---- next-weight prefetch (include/upk.h pf_next): lines of pf[0 .. pf_lines * 128) are touched by this launch's workgroups
   const char* pf;
   int pf_lines;
-  int pf_self;  // (dev experiment, UPK_SELF_PREFETCH=1: the workgroups of an XCD that share a weight slice touch it cooperatively up front)
 };
 
 // Split-K partial slabs ([split][M][n_pad] in the caller's workspace, IgemmArgs::partial).  fp16: the partial sums are
 // rounded once on their way out and added in fp32 by the reduce pass, in slab order (deterministic as before) — half
 // the bytes of the fp32 slabs, which cost 80 us of the forward on their way out alone (phase ablation,
 // profiles/r04_forward_phase_ablation_igemm_ws.txt).  Error: one extra fp16 rounding per partial, ~|y| 2^-11 in
-// total for z partials of magnitude |y| / sqrt z — the size of the output's own rounding.  -DUPK_SLAB_F32: fp32 slabs.
-#ifdef UPK_SLAB_F32
-typedef float slab_t;
-typedef f32x4 slab4;
-#else
+// total for z partials of magnitude |y| / sqrt z — the size of the output's own rounding.
 typedef f16 slab_t;
 typedef f16x4 slab4;
-#endif
 // write-through (sc1): the partials are on their way to memory when the kernel ends instead of being written back
 // at the boundary (MI355X_MICROARCH.md publish-large / boundary); same-box A/B on the forward: 2.946 -> 2.941 ms
 __device__ __forceinline__ void slab_store(slab_t* p, f32x4 v) {
-#ifdef UPK_SLAB_F32
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-#else
   // saturating: a partial beyond the fp16 range (K slices of large, cancelling activations) stays finite, so the fp32 sum
   // of the slices is off by the clipped amount instead of inf / nan (v_med3_f32: one VALU instruction per element)
   const f16x4 h = {(f16)__builtin_amdgcn_fmed3f(v[0], -65504.f, 65504.f), (f16)__builtin_amdgcn_fmed3f(v[1], -65504.f, 65504.f),
                    (f16)__builtin_amdgcn_fmed3f(v[2], -65504.f, 65504.f), (f16)__builtin_amdgcn_fmed3f(v[3], -65504.f, 65504.f)};
   asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(p), "v"(h) : "memory");
-#endif
 }
 __device__ __forceinline__ f32x4 slab_load4(const slab_t* p) {
   const slab4 v = *(const slab4*)p;

@@ -25,9 +25,7 @@ namespace upkd {
 namespace {
 
 constexpr int ML_NW = 8;
-#ifndef UPK_MLP_SLICES
-#define UPK_MLP_SLICES 2  // (1 in dev builds: one h slice and a second barrier per pass — the A/B of DESIGN.md 26)
-#endif
+constexpr int ML_SLICES = 2;  // h slices in LDS (one slice and a second barrier per pass lost the A/B of DESIGN.md 26)
 
 struct MlpArgs {
   const f16* x;      // t2 [M, ldx] (un-normalised residual stream)
@@ -348,7 +346,7 @@ __global__ __launch_bounds__(512) void mlp_stream_kernel(const MlpArgs s) {
   constexpr int NK1 = 7;            // K chunks of a GEGLU pass (c = 224: n_pad <= 256 leaves no other member of the family)
   constexpr int NS = PW / 64;       // hidden chunks per pass = K chunks of the second GEMM per slice
   constexpr int S = NK1 + NS;
-  constexpr int NSL = UPK_MLP_SLICES;
+  constexpr int NSL = ML_SLICES;
   static_assert(RD >= 1 && RD <= NK1, "the first RD steps of a pass are w1 chunks (t2 chunks behind the last pass)");
   extern __shared__ __attribute__((aligned(16))) f16 smem[];
   ML_PIN(s.x); ML_PIN(s.w1); ML_PIN(s.w2); ML_PIN(s.zero); ML_PIN(s.b1); ML_PIN(s.u1); ML_PIN(s.b2); ML_PIN(s.res);
@@ -517,7 +515,6 @@ __global__ __launch_bounds__(512) void mlp_stream_kernel(const MlpArgs s) {
       refill(tc);
       __builtin_amdgcn_sched_barrier(0);
     });
-    if constexpr (NSL == 1) __syncthreads();  // (the slice is free again)
   }
 
   // ---- 5. the t2 chunks of the second GEMM from the resident tile; epilogue: bias, residual, GroupNorm partials
@@ -610,7 +607,7 @@ static int mlp_form(const upk_mlp_desc* d, int* stream) {
 
 // LDS of a launch: the resident form keeps [h | t2] (nh + nch1 chunks), the streaming form t2 and two 4-chunk slices of h
 static size_t mlp_lds_bytes(int nch1, int nh, int n1, int bm, int stream) {
-  return (size_t)(stream ? nch1 + 4 * UPK_MLP_SLICES : nch1 + nh) * bm * 64 + (size_t)bm * 8 + (size_t)n1 * 8;
+  return (size_t)(stream ? nch1 + 4 * ML_SLICES : nch1 + nh) * bm * 64 + (size_t)bm * 8 + (size_t)n1 * 8;
 }
 
 extern "C" int upk_geglu_mlp_supported(upk_ctx* ctx, const upk_mlp_desc* d) {

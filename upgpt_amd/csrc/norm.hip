@@ -15,8 +15,6 @@
 // strided slice — was measured at 21.8 us vs 14.6 us for this pair on the 16x16 / 32x32 UNet shapes: the
 // 8-byte strided lanes from 64-256 blocks lose to two fully coalesced passes.  At <= 64 pixels per sample the
 // (sample, group) fits the registers of one workgroup and one launch wins: gn_onepass_kernel.)
-#include <stdlib.h>
-
 #include "common.h"
 
 namespace {
@@ -511,14 +509,10 @@ static int gn_launch(upk_ctx* ctx, const void* x1, int c1, int ld1, const void* 
                       (c2 != 0 && (!stats_ws2 || cp_ld2 < c2 || cp_nblk2 <= 0 || cp_nblk2 > GN_MAX_CHUNKS))))
     return upk_fail(ctx, UPK_EINVAL, "groupnorm apply: channel partials need stats_ld >= channels and 0 < nblk <= %d for "
                     "every source", GN_MAX_CHUNKS);
-  static const bool fold1 = getenv("UPK_GN_FOLD1") && atoi(getenv("UPK_GN_FOLD1"));  // dev: timing bound of a free partial fold (WRONG results)
-  if (fold1 && a.cp_nblk > 1) a.cp_nblk = 1;
-  if (fold1 && a.cp_nblk2 > 1) a.cp_nblk2 = 1;
   upk_prof_scope prof(ctx, UPK_CLS_GN, stream);
   int rc = UPK_OK;
   // small feature maps: statistics and normalisation in ONE launch (gn_onepass_kernel)
-  static const bool onepass_off = getenv("UPK_GN_ONEPASS") && !atoi(getenv("UPK_GN_ONEPASS"));  // dev: A/B
-  if (with_stats && with_apply && hw <= 64 && !onepass_off) {
+  if (with_stats && with_apply && hw <= 64) {
     const int v = !(a.cpg & 7) ? 8 : (!(a.cpg & 3) ? 4 : (!(a.cpg & 1) ? 2 : 0));
     const int nv = v ? (hw * (a.cpg / v) + 255) / 256 : 0;
     const dim3 grid(groups, batch);
@@ -540,9 +534,7 @@ static int gn_launch(upk_ctx* ctx, const void* x1, int c1, int ld1, const void* 
   // dependent memory round trips, so it needs co-resident blocks, not long per-block loops)
   // ... up to ~4096 blocks: beyond that (VAE decoder: 64 K - 524 K rows) a block's fixed part — folding the partial
   // statistics, gamma / beta, the scale / shift table — outweighs its 4 KB of data
-  static const int blk_elems = getenv("UPK_GN_BLOCK_ELEMS") ? atoi(getenv("UPK_GN_BLOCK_ELEMS")) : 2048;  // dev
-  int rows = (blk_elems + C - 1) / C;
-  if (rows < 1) rows = 1;
+  int rows = (2048 + C - 1) / C;
   const long rows_big = ((long)hw * batch + 4095) / 4096;
   if (rows_big > rows) rows = (int)(rows_big < 4096 ? rows_big : 4096);
   const int blocks = (hw + rows - 1) / rows;

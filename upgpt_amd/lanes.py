@@ -19,7 +19,6 @@ threads are serialised against each other (_lib.host_io; a steady-state sample()
 nothing).  DESIGN.md 13.
 """
 import contextlib
-import os
 import threading
 import time
 
@@ -105,11 +104,7 @@ class LanePool:
                 get_context(self.device, lane=i)
         self.queue_probe = "n/a"
         # a one-lane pool is exactly the serial path (caller's stream); with more lanes every lane has a stream of its own
-        # (UPGPT_LANE0_MAIN=1: lane 0 on the caller's stream instead)
-        self.lane0_main = os.environ.get("UPGPT_LANE0_MAIN", "0") == "1"
-        k = self.n - 1 if self.lane0_main else self.n
-        self.streams = [None] * self.n if not self.gpu or self.n == 1 else (
-            ([None] if self.lane0_main else []) + self._distinct_queue_streams(k, with_main=self.lane0_main))
+        self.streams = [None] * self.n if not self.gpu or self.n == 1 else self._distinct_queue_streams(self.n)
         self._xstream = torch.cuda.Stream(device=self.device) if self.gpu and self.n > 1 else None
 
     # ---- stream -> hardware queue placement
@@ -128,8 +123,8 @@ class LanePool:
         two = min(run([sa, sb]) for _ in range(3))
         return two < 1.5 * one, one
 
-    def _distinct_queue_streams(self, k, candidates=12, with_main=True):
-        """k streams that share a hardware queue neither with the caller's stream nor with each other.  The runtime
+    def _distinct_queue_streams(self, k, candidates=12):
+        """k streams that do not share a hardware queue with each other.  The runtime
         multiplexes its streams onto a few hardware queues (4 by default) in creation order; two lanes that land on one
         queue take turns instead of overlapping (measured: 5.70 ms for two forwards against 4.25 ms on two queues,
         scripts/stream_queues.py), so the pool measures instead of trusting the order.  Falls back to fresh streams when
@@ -146,7 +141,7 @@ class LanePool:
                 for c in cands:
                     if len(chosen) == k:
                         break
-                    if all(self._overlap(o, c, cycles)[0] for o in ([main] if with_main else []) + chosen):
+                    if all(self._overlap(o, c, cycles)[0] for o in chosen):
                         chosen.append(c)
             except Exception:
                 chosen = []
