@@ -366,13 +366,13 @@ def test_plan_close_releases_the_ddpm_state(monkeypatch):
     unet = m.model.diffusion_model
     m.p_sample_loop(cond, (2, C) + HW, x_T=inp["x_T"].cuda(), verbose=False, timesteps=20,
                     normals_sequence=inp["noise"])
-    plans = [pl for pl in unet._plans.values() if getattr(pl, "_ddpm_state", None) is not None]
+    plans = [pl for pl in unet._plans.values() if ("ddpm", False) in pl.sampler_states]
     assert plans
-    graphs = [g for pl in plans for g in pl._ddpm_state.graphs.values()]
+    graphs = [g for pl in plans for g in pl.sampler_state("ddpm", C).graphs.values()]
     assert graphs
     destroyed = []
     orig = _lib.Context.graph_destroy
     monkeypatch.setattr(_lib.Context, "graph_destroy", lambda self, g: (destroyed.append(g), orig(self, g))[1])
     unet.invalidate()
-    assert all("_ddpm_state" not in pl.__dict__ for pl in plans)
+    assert all(not pl.sampler_states for pl in plans)
     assert all(any(g is d for d in destroyed) for g in graphs)

@@ -177,6 +177,7 @@ def test_a_warm_keyed_call_never_enters_host_io(monkeypatch):
     lock) the keyed fast path does not enter it; the unkeyed call at eta = 1 does, for its draws."""
     import contextlib
 
+    from upgpt_amd import chain as chain_mod
     from upgpt_amd import ddim as ddim_mod
     from upgpt_amd import engine
     model = get_model()
@@ -196,7 +197,7 @@ def test_a_warm_keyed_call_never_enters_host_io(monkeypatch):
     with L.shared_chip(2):  # (host_io() is live, as inside a lane of a pool)
         warm = run(noise_keys=K)[0]
         assert engine.L is L  # (the graph capture reaches the lock as L.host_io)
-        for mod in (L, ddim_mod):
+        for mod in (L, ddim_mod, chain_mod):
             monkeypatch.setattr(mod, "host_io", counted)
         again = run(noise_keys=K)[0]
         assert not entered, "a warm keyed call took the host_io lock"

@@ -4,20 +4,20 @@ progressive_denoising) with the reference's signatures and return values.
 
 Fast path: the chain runs on a sampler-mode UNetPlan with one timestep-embedding row per DDPM step; each step — UNet
 forward, posterior update (upk_ddpm_step_f32), optional q_sample blend of a mask, refresh of the stem input, step
-counter — is replayed from captured HIP graphs (engine.SamplerState, up to ddim.STEPS_PER_GRAPH steps per graph).  All
-random draws happen before the loop, one call per draw in the reference's order, so the device generator ends where the
-reference leaves it.  Everything the fast path cannot take (tensor conditioning, score_corrector, noise_dropout) goes
-step by step through p_sample.
+counter — is replayed from captured HIP graphs (engine.SamplerState kind "ddpm", launched by chain.run: up to
+ddim.STEPS_PER_GRAPH steps per graph).  All random draws happen before the loop, one call per draw in the reference's order,
+so the device generator ends where the reference leaves it.  Everything the fast path cannot take (tensor conditioning,
+score_corrector, noise_dropout) goes step by step through p_sample.
 """
 import numbers
 
 import numpy as np
 import torch
 
+from . import chain, rng
 from . import ddim as _ddim
-from . import rng
 from ._check import require
-from ._lib import DDPM_CLIP, DDPM_X0, get_context, host_io
+from ._lib import DDPM_CLIP, DDPM_X0, get_context
 from .ddim import noise_like
 from .schedule import ddpm_coefficient_table, extract_into_tensor
 
@@ -210,10 +210,7 @@ class AncestralSampling:
         device = self.betas.device
         b = shape[0]
         keyed = noise_keys is not None
-        if x_T is not None:
-            img = x_T
-        else:
-            img = rng.randn(noise_keys, shape, rng.STREAM_XT) if keyed else torch.randn(shape, device=device)
+        img = x_T if x_T is not None else chain.start_latent(None, noise_keys, shape, device)  # (a given x_T stays where it is)
         intermediates = [] if log_x0 else [img]
         for k, i in enumerate(reversed(range(0, T))):
             ts = torch.full((b,), i, device=device, dtype=torch.long)
@@ -249,23 +246,13 @@ class AncestralSampling:
         masked = mask is not None
         keyed = noise_keys is not None
         with torch.cuda.device(dev):
-            st = getattr(plan, "_ddpm_state", None)
-            if st is None:
-                from .engine import SamplerState
-                st = plan._ddpm_state = SamplerState(plan, C, ddpm=True)
-            st.ddpm_flags = (DDPM_X0 if self.parameterization == "x0" else 0) | (DDPM_CLIP if self.clip_denoised else 0)
-            st.masked = masked
+            st = plan.sampler_state("ddpm", C)
+            st.set_variant(((DDPM_X0 if self.parameterization == "x0" else 0) | (DDPM_CLIP if self.clip_denoised else 0),
+                            masked))
             order = np.arange(T)[::-1].copy()  # loop order: timesteps T-1 ... 0 (no +1 as in DDIM)
             rkey = ("ddpm", order.astype(np.float32).tobytes())
-            # every call draws (or copies in) T rows of noise, so it always takes the upload lock, as DDIM does whenever
-            # it has noise to draw (_lib.host_io).  (Keyed noise needs no lock, but this call uploads its coefficient and
-            # temperature tables every time, so it keeps it.)
-            with host_io():
-                if x_T is not None:
-                    img = x_T.to(dev, torch.float32)
-                else:
-                    img = rng.randn(noise_keys, shape, rng.STREAM_XT) if keyed else torch.randn(shape, device=dev)
-                st.x.copy_(img)
+            with chain.upload_lock(True):  # (always: T rows of noise, or with keys still the coefficient and temperature rows)
+                st.x.copy_(chain.start_latent(x_T, noise_keys, shape, dev, torch.float32))
                 plan.load_sampler_inputs(st.x, c_concat, c_cross, unet.in_channels, rkey, order.astype(np.float32))
                 st.coefs.copy_(ddpm_coefficient_table(self, order))
                 # the draws of the reference, in its order: per step noise_like(x.shape) (also at t = 0, where the row
@@ -298,19 +285,11 @@ class AncestralSampling:
                 plan.step.zero_()
                 plan.prep.run()
             intermediates = [] if log_x0 else [st.x.clone()]
-            # steps whose result the host looks at end a graph (as in ddim.py); the others run up to STEPS_PER_GRAPH to
-            # a graph launch
             watched = callback is not None or img_callback is not None
-            logged = lambda k: (T - 1 - k) % log_every_t == 0 or k == 0
-            k = 0
-            while k < T:
-                n = 1
-                while n < _ddim.STEPS_PER_GRAPH and k + n < T and not (watched or logged(k + n - 1)):
-                    n += 1
-                st.launch(True, 1.0, n)
-                k += n
-                i = T - k
-                if logged(k - 1):
+            logged = chain.logged_at(T, log_every_t)
+            for k in chain.run(st, T, _ddim.STEPS_PER_GRAPH, watched, logged, True):
+                i = T - 1 - k  # (the reference's loop variable is the timestep: what it logs by and hands to the callbacks)
+                if logged(k):
                     intermediates.append((st.pred_x0 if log_x0 else st.x).clone())
                 if callback:
                     callback(i)

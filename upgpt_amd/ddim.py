@@ -12,14 +12,17 @@ per step from Python (ddim.py:140-203).
 The editing calls run on the same captured loop (upk_ddim_step_edit_f32): sample(mask=, x0=)
 (inpainting), decode (img2img) and ddim_sampling(timesteps=) — the last two as chains that
 start at a later row of the same S-row tables.
+
+The loop itself — grouping of steps into graph launches, the start latent, the lock rule of the part in front of it —
+is chain.py's, shared with PLMS, DDPM and DPM-Solver++; this class also holds what its subclasses share with it: the
+schedule cache (_ensure_schedule), the shortened schedule (_subset) and the guided model evaluation (_guided_eps).
 """
-import contextlib
 import os
 
 import numpy as np
 import torch
 
-from . import rng
+from . import chain, rng
 from ._check import require
 from ._lib import host_io
 from .schedule import (ddim_coefficient_table, extract_into_tensor, make_ddim_sampling_parameters,
@@ -101,14 +104,8 @@ class DDIMSampler(object):
             cbs = (first[0] if isinstance(first, (list, tuple)) else first).shape[0]
             if cbs != batch_size:
                 print(f"Warning: Got {cbs} conditionings but batch-size is {batch_size}")
-        # the schedule tables of (S, eta) are kept between calls (the reference rebuilds and re-uploads them every time,
-        # ddim.py:86): with several batches in flight a blocking upload per call serialises the lanes (_lib.host_io)
-        acp = self.model.alphas_cumprod
-        key = (int(S), float(eta), id(self.model), acp.data_ptr(), int(getattr(acp, "_version", 0)), str(acp.device))
-        if verbose or getattr(self, "_sched_key", None) != key:
-            with host_io():
-                self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
-            self._sched_key = key
+        self._ensure_schedule((int(S), float(eta)), lambda: self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose),
+                              verbose)
         C, H, W = shape
         size = (batch_size, C, H, W)
         print(f"Data shape for DDIM sampling is {size}, eta {eta}")
@@ -119,6 +116,42 @@ class DDIMSampler(object):
                                   log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning,
                                   normals_sequence=normals_sequence, noise_keys=noise_keys)
+
+    def _ensure_schedule(self, key_extra, build, verbose=False):
+        """The schedule tables of an unchanged key are kept between calls (the reference rebuilds and re-uploads them every
+        time, ddim.py:86): with several batches in flight a blocking upload per call serialises the lanes (_lib.host_io).
+        key_extra: what the sampler's tables depend on besides the model's alphas; build: its make_schedule call.
+        verbose rebuilds, for the lines make_schedule prints."""
+        acp = self.model.alphas_cumprod
+        key = tuple(key_extra) + (id(self.model), acp.data_ptr(), int(getattr(acp, "_version", 0)), str(acp.device))
+        if verbose or getattr(self, "_sched_key", None) != key:
+            with host_io():
+                build()
+            self._sched_key = key
+
+    def _subset(self, timesteps):
+        """`timesteps` as the sampling loops take it: None = the whole schedule, a count = the reference's shortened
+        schedule (ddim.py:128-130; its `- 1` is kept: a count of n gives n - 1 steps)."""
+        if timesteps is None:
+            return self.ddim_timesteps
+        subset_end = int(min(timesteps / self.ddim_timesteps.shape[0], 1) * self.ddim_timesteps.shape[0]) - 1
+        return self.ddim_timesteps[:subset_end]
+
+    def _guided_eps(self, x, t, c, scale, uc, score_corrector=None, corrector_kwargs=None, combine=True):
+        """The model's eps at (x, t): one evaluation, or with guidance one over [uncond ; cond] (ddim.py:173-178) combined
+        as e_u + scale * (e - e_u), then the score corrector.  combine=False (DPM-Solver++ without a corrector) hands
+        back the uncombined [uncond ; cond] rows of a guided evaluation: its step kernel combines them."""
+        if uc is None or scale == 1.:
+            e_t = self.model.apply_model(x, t, c)
+        else:
+            e_t = self.model.apply_model(torch.cat([x] * 2), torch.cat([t] * 2), self._cat_cond(uc, c))
+            if combine:
+                e_t_uncond, e_t = e_t.chunk(2)
+                e_t = e_t_uncond + scale * (e_t - e_t_uncond)
+        if score_corrector is not None:
+            require(self.model.parameterization == "eps", "classifier-free guidance / score correction needs an eps-parameterised model", NotImplementedError)
+            e_t = score_corrector.modify_score(self.model, e_t, x, t, c, **(corrector_kwargs or {}))
+        return e_t
 
     # ------------------------------------------------------------------ fast path
     def _fast_ok(self, cond, ddim_use_original_steps, quantize_denoised, mask, noise_dropout, score_corrector,
@@ -165,16 +198,11 @@ class DDIMSampler(object):
         plan = unet.plan(2 * b if cfg else b, H, W, c_cross.shape[1], S, "sampler")
         dev = plan.dev
         with torch.cuda.device(dev):
-            attr = "_sampler_state_cfg" if cfg else "_sampler_state"
-            st = getattr(plan, attr, None)
-            if st is None:
-                from .engine import SamplerState
-                st = SamplerState(plan, C, cfg=cfg)
-                setattr(plan, attr, st)
+            st = plan.sampler_state("ddim", C, cfg)
             order = np.arange(S)[::-1].copy()  # loop order: descending DDIM index
             sig = torch.as_tensor(np.asarray(self.ddim_sigmas, dtype=np.float64)).float()[torch.as_tensor(order)]
             with_noise = bool((sig[k:] != 0).any())
-            st.edit = "masked" if masked else "plain" if (edit or k > 0) else None
+            st.set_variant("masked" if masked else "plain" if (edit or k > 0) else None)
             f64b = lambda v: np.asarray(v, dtype=np.float64).tobytes()
             # upload-once caches.  The timestep rows live on the PLAN (one buffer shared by the DDIM / PLMS, guided / unguided
             # sampler states of that plan), so their key does too; the coefficient table is this state's own
@@ -186,15 +214,9 @@ class DDIMSampler(object):
             skey = (ckey, float(temperature))
             fresh_scale = keyed and with_noise and getattr(st, "_nscale_key", None) != skey
             fresh = fresh_rows or fresh_coefs or fresh_scale
-            on_host = any(t is not None and torch.is_tensor(t) and not t.is_cuda for t in (x_T, c_concat, c_cross, mask, x0))
-            # uploads from the host never overlap another lane's graph capture (_lib.host_io); a call with everything on
-            # the device and an unchanged schedule uploads nothing and takes no lock
-            with (host_io() if (fresh or on_host or (with_noise and not keyed)) else contextlib.nullcontext()):
-                if x_T is not None:
-                    img = x_T.to(dev, torch.float32)
-                else:
-                    img = rng.randn(noise_keys, shape, rng.STREAM_XT) if keyed else torch.randn(shape, device=dev)
-                st.x.copy_(img)
+            on_host = chain.on_host(x_T, c_concat, c_cross, mask, x0)
+            with chain.upload_lock(fresh or on_host or (with_noise and not keyed)):
+                st.x.copy_(chain.start_latent(x_T, noise_keys, shape, dev, torch.float32))
                 if masked:
                     keep, emask, _ = st.ensure_edit()
                     x0 = x0.to(dev)
@@ -243,22 +265,15 @@ class DDIMSampler(object):
                 plan.prep.run()
             intermediates = {"x_inter": [first], "pred_x0": [first.clone()]}
             print(f"Running DDIM Sampling with {T} timesteps")
-            # steps whose result the host looks at (callbacks, logged intermediates: ddim.py:139-147) end a graph; the
-            # steps between them run up to STEPS_PER_GRAPH to a graph launch
+            # (steps whose result the host looks at — callbacks, logged intermediates: ddim.py:139-147 — end a graph)
             watched = callback is not None or img_callback is not None
-            logged = lambda i: log_every_t is not None and ((T - i - 1) % log_every_t == 0 or i == 0)
-            i = 0
-            while i < T:
-                n = 1
-                while n < STEPS_PER_GRAPH and i + n < T and not (watched or logged(i + n - 1)):
-                    n += 1
-                st.launch(with_noise, cfg_scale, n)
-                i += n
+            logged = chain.logged_at(T, log_every_t)
+            for i in chain.run(st, T, STEPS_PER_GRAPH, watched, logged, with_noise, cfg_scale):
                 if callback:
-                    callback(i - 1)
+                    callback(i)
                 if img_callback:
-                    img_callback(st.pred_x0.clone(), i - 1)
-                if logged(i - 1):
+                    img_callback(st.pred_x0.clone(), i)
+                if logged(i):
                     # (masked: st.x already holds the blend for the next step; the reference logs the unblended value)
                     intermediates["x_inter"].append((st.x_plain if masked else st.x).clone())
                     intermediates["pred_x0"].append(st.pred_x0.clone())
@@ -277,11 +292,10 @@ class DDIMSampler(object):
         keyed = noise_keys is not None
         device = self.model.betas.device
         b = shape[0]
-        if timesteps is None:
-            timesteps = self.ddpm_num_timesteps if ddim_use_original_steps else self.ddim_timesteps
-        elif not ddim_use_original_steps:
-            subset_end = int(min(timesteps / self.ddim_timesteps.shape[0], 1) * self.ddim_timesteps.shape[0]) - 1
-            timesteps = self.ddim_timesteps[:subset_end]
+        if ddim_use_original_steps:
+            timesteps = self.ddpm_num_timesteps if timesteps is None else timesteps
+        else:
+            timesteps = self._subset(timesteps)
 
         if self._fast_ok(cond, ddim_use_original_steps, quantize_denoised, mask, noise_dropout, score_corrector,
                          unconditional_guidance_scale, unconditional_conditioning) \
@@ -291,10 +305,7 @@ class DDIMSampler(object):
                                        uc=unconditional_conditioning, mask=mask, x0=x0, noise_keys=noise_keys)
 
         # general path: one apply_model + one fused update kernel per step, driven from Python
-        if x_T is not None:
-            img = x_T.to(device)
-        else:
-            img = rng.randn(noise_keys, shape, rng.STREAM_XT) if keyed else torch.randn(shape, device=device)
+        img = chain.start_latent(x_T, noise_keys, shape, device)
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         time_range = reversed(range(0, timesteps)) if ddim_use_original_steps else np.flip(timesteps)
         total_steps = timesteps if ddim_use_original_steps else timesteps.shape[0]
@@ -349,19 +360,8 @@ class DDIMSampler(object):
                       unconditional_guidance_scale=1., unconditional_conditioning=None, noise=None, noise_keys=None):
         require(noise_keys is None or not repeat_noise,
                 "repeat_noise shares one draw over the batch; noise_keys gives every sample its own", ValueError)
-        b, device = x.shape[0], x.device
-        if unconditional_conditioning is None or unconditional_guidance_scale == 1.:
-            e_t = self.model.apply_model(x, t, c)
-        else:
-            x_in = torch.cat([x] * 2)
-            t_in = torch.cat([t] * 2)
-            c_in = self._cat_cond(unconditional_conditioning, c)
-            e_t_uncond, e_t = self.model.apply_model(x_in, t_in, c_in).chunk(2)
-            e_t = e_t_uncond + unconditional_guidance_scale * (e_t - e_t_uncond)
-        if score_corrector is not None:
-            require(self.model.parameterization == "eps", "classifier-free guidance / score correction needs an eps-parameterised model", NotImplementedError)
-            e_t = score_corrector.modify_score(self.model, e_t, x, t, c, **corrector_kwargs)
-
+        e_t = self._guided_eps(x, t, c, unconditional_guidance_scale, unconditional_conditioning, score_corrector,
+                               corrector_kwargs)
         if quantize_denoised:
             raise NotImplementedError("quantize_denoised needs a VQ first stage (not on the UPGPT path)")
         return self._ddim_update(x, e_t, index, use_original_steps=use_original_steps, temperature=temperature,

@@ -8,17 +8,15 @@ grid the last steps jump so far in logSNR that the second-order term gains nothi
 and `"quad"` still take the reference's grids.
 
 Fast path (DDIMSampler._fast_ok's conditions, no mask, the whole chain): the captured HIP graph UNet body ->
-upk_dpmpp_2m_step_f32 of engine.SamplerState(dpm=True), up to ddim.STEPS_PER_GRAPH steps per graph, S replays in all;
-guidance is combined inside the step kernel.  Anything else (mask / x0, decode, a shortened chain, a score corrector, noise
-dropout) runs on the general path: one apply_model per step from Python and the same kernel launched eagerly.
+upk_dpmpp_2m_step_f32 of engine.SamplerState kind "dpm", launched by chain.run: up to ddim.STEPS_PER_GRAPH steps per graph,
+S replays in all; guidance is combined inside the step kernel.  Anything else (mask / x0, decode, a shortened chain, a score
+corrector, noise dropout) runs on the general path: one apply_model per step from Python and the same kernel launched eagerly.
 """
-import contextlib
-
 import numpy as np
 import torch
 
+from . import chain, rng
 from . import ddim as _ddim
-from . import rng
 from ._check import require
 from ._lib import get_context, host_io
 from .ddim import DDIMSampler
@@ -59,13 +57,8 @@ class DPMSolverSampler(DDIMSampler):
             raise ValueError("DPM-Solver++(2M) is deterministic: eta must be 0 (got %r)" % (eta,))
         require(getattr(self.model, "parameterization", "eps") == "eps",
                 "DPM-Solver++(2M) here takes an eps-parameterised model", NotImplementedError)
-        acp = self.model.alphas_cumprod  # (tables of an unchanged key are kept between calls, as in DDIMSampler.sample)
-        key = (int(S), str(discretize), int(order), lower_order_final, id(self.model), acp.data_ptr(),
-               int(getattr(acp, "_version", 0)), str(acp.device))
-        if verbose or getattr(self, "_sched_key", None) != key:
-            with host_io():
-                self.make_schedule(S, discretize, 0., verbose, order=order, lower_order_final=lower_order_final)
-            self._sched_key = key
+        self._ensure_schedule((int(S), str(discretize), int(order), lower_order_final), lambda: self.make_schedule(
+            S, discretize, 0., verbose, order=order, lower_order_final=lower_order_final), verbose)
         C, H, W = shape
         size = (batch_size, C, H, W)
         print(f"Data shape for DPM-Solver++(2M) sampling is {size}")
@@ -84,21 +77,13 @@ class DPMSolverSampler(DDIMSampler):
         rng.check_keys(noise_keys, shape[0])
         if quantize_denoised:
             raise NotImplementedError("quantize_denoised needs a VQ first stage (not on the UPGPT path)")
-        if timesteps is None:
-            timesteps = self.ddim_timesteps
-        else:
-            subset_end = int(min(timesteps / self.ddim_timesteps.shape[0], 1) * self.ddim_timesteps.shape[0]) - 1
-            timesteps = self.ddim_timesteps[:subset_end]
+        timesteps = self._subset(timesteps)
         if mask is None and len(timesteps) == len(self.ddim_timesteps) and \
                 self._fast_ok(cond, False, quantize_denoised, None, noise_dropout, score_corrector,
                               unconditional_guidance_scale, unconditional_conditioning):
             return self._fast_dpm(cond, shape, x_T, callback, img_callback, log_every_t, unconditional_guidance_scale,
                                   unconditional_conditioning, noise_keys)
-        device = self.model.betas.device
-        if x_T is not None:
-            img = x_T.to(device)
-        else:
-            img = torch.randn(shape, device=device) if noise_keys is None else rng.randn(noise_keys, shape, rng.STREAM_XT)
+        img = chain.start_latent(x_T, noise_keys, shape, self.model.betas.device)
         return self._general(img, cond, timesteps, callback, img_callback, log_every_t, mask, x0, score_corrector,
                              corrector_kwargs, unconditional_guidance_scale, unconditional_conditioning, noise_keys)
 
@@ -137,18 +122,10 @@ class DPMSolverSampler(DDIMSampler):
                 require(x0 is not None, "mask given without x0", ValueError)
                 qn = {} if noise_keys is None else {"noise": rng.randn(noise_keys, shape, rng.STREAM_QSAMPLE, row0=k + i)}
                 x = (self.model.q_sample(x0, ts, **qn) * mask + (1. - mask) * x).float().contiguous()
-            in_kernel = False
-            if not guided:
-                e = self.model.apply_model(x, ts, cond)
-            else:
-                e2 = self.model.apply_model(torch.cat([x] * 2), torch.cat([ts] * 2), self._cat_cond(uc, cond))
-                if score_corrector is None:
-                    e, in_kernel = e2, True  # ([uncond ; cond]: combined inside the step kernel, as on the fast path)
-                else:
-                    e_u, e = e2.chunk(2)
-                    e = e_u + cfg_scale * (e - e_u)
-            if score_corrector is not None:
-                e = score_corrector.modify_score(self.model, e, x, ts, cond, **(corrector_kwargs or {}))
+            # ([uncond ; cond] of a guided evaluation is combined inside the step kernel, as on the fast path; a score
+            # corrector needs the combined eps first)
+            in_kernel = guided and score_corrector is None
+            e = self._guided_eps(x, ts, cond, cfg_scale, uc, score_corrector, corrector_kwargs, combine=not in_kernel)
             pred_x0 = torch.empty_like(x)
             with torch.cuda.device(device):
                 ctx.dpmpp_2m_step(x, e.float().contiguous(), coefs, rows[k + i:k + i + 1], x0_old, pred_x0, None, 0, b, C, hw,
@@ -174,7 +151,6 @@ class DPMSolverSampler(DDIMSampler):
 
     # ------------------------------------------------------------------ fast path
     def _fast_dpm(self, cond, shape, x_T, callback, img_callback, log_every_t, cfg_scale, uc, noise_keys=None):
-        from .engine import SamplerState
         model = self.model
         unet = model.model.diffusion_model
         b, C, H, W = shape
@@ -186,24 +162,17 @@ class DPMSolverSampler(DDIMSampler):
         plan = unet.plan(2 * b if cfg else b, H, W, c_cross.shape[1], S, "sampler")
         dev = plan.dev
         with torch.cuda.device(dev):
-            attr = "_dpm_state_cfg" if cfg else "_dpm_state"
-            st = getattr(plan, attr, None)
-            if st is None:
-                st = SamplerState(plan, C, cfg=cfg, dpm=True)
-                setattr(plan, attr, st)
+            st = plan.sampler_state("dpm", C, cfg)
             t_desc = np.asarray(self.ddim_timesteps)[::-1].astype(np.float32)
             # upload-once caches, as in DDIMSampler._fast_sampling: the timestep rows belong to the plan, the table to the state
             rkey = ("dpm", t_desc.tobytes())
             ckey = self.dpm_coefs.numpy().tobytes()
             fresh_coefs = getattr(st, "_coef_key", None) != ckey
             fresh = fresh_coefs or getattr(plan, "_t_rows_key", None) != rkey
-            on_host = any(t is not None and torch.is_tensor(t) and not t.is_cuda for t in (x_T, c_concat, c_cross))
-            with (host_io() if (fresh or on_host or (x_T is None and noise_keys is None)) else contextlib.nullcontext()):
-                if x_T is not None:
-                    img = x_T.to(dev, torch.float32)
-                else:
-                    img = torch.randn(shape, device=dev) if noise_keys is None else rng.randn(noise_keys, shape, rng.STREAM_XT)
-                st.x.copy_(img)
+            on_host = chain.on_host(x_T, c_concat, c_cross)
+            keyed = noise_keys is not None
+            with chain.upload_lock(fresh or on_host or (x_T is None and not keyed)):
+                st.x.copy_(chain.start_latent(x_T, noise_keys, shape, dev, torch.float32))
                 if fresh_coefs:
                     st.coefs.copy_(self.dpm_coefs)
                     st._coef_key = ckey
@@ -214,21 +183,14 @@ class DPMSolverSampler(DDIMSampler):
             first = st.x.clone()
             intermediates = {"x_inter": [first], "pred_x0": [first.clone()]}
             print(f"Running DPM-Solver++(2M) Sampling with {S} timesteps")
-            # steps the host looks at (callbacks, logged intermediates) end a graph, as in ddim.py
             watched = callback is not None or img_callback is not None
-            logged = lambda i: log_every_t is not None and ((S - i - 1) % log_every_t == 0 or i == 0)
-            i = 0
-            while i < S:
-                n = 1
-                while n < _ddim.STEPS_PER_GRAPH and i + n < S and not (watched or logged(i + n - 1)):
-                    n += 1
-                st.launch(False, cfg_scale, n)
-                i += n
+            logged = chain.logged_at(S, log_every_t)
+            for i in chain.run(st, S, _ddim.STEPS_PER_GRAPH, watched, logged, False, cfg_scale):
                 if callback:
-                    callback(i - 1)
+                    callback(i)
                 if img_callback:
-                    img_callback(st.pred_x0.clone(), i - 1)
-                if logged(i - 1):
+                    img_callback(st.pred_x0.clone(), i)
+                if logged(i):
                     intermediates["x_inter"].append(st.x.clone())
                     intermediates["pred_x0"].append(st.pred_x0.clone())
             return st.x.clone(), intermediates

@@ -58,6 +58,7 @@ class UNetPlan(Emitter):
         self.gn_ws = self.alloc(max(64, ctx.groupnorm_ws_bytes(B, H * W) // 4), dtype=torch.float32)
         self.rowvecs = {}
         self.kv = {}
+        self.sampler_states = {}  # (kind, guided) -> SamplerState (sampler_state())
         self.prep = Program(ctx)
         self.body = Program(ctx)
         self._emit_prep()
@@ -226,14 +227,26 @@ class UNetPlan(Emitter):
         self.conv(P, x, self.pk.w["out.2"], nchw_out=self.eps, gn=(*self.pk.v["out.0"], 1e-5, True, self.gn_ws))
 
     # ---- host-facing helpers
+    def sampler_state(self, kind, channels, cfg=False):
+        """The plan's SamplerState of (kind, guided or not), made on first use: what a sampler's fast path runs its chain on."""
+        st = self.sampler_states.get((kind, bool(cfg)))
+        if st is None:
+            st = self.sampler_states[(kind, bool(cfg))] = SamplerState(self, channels, kind, cfg)
+        return st
+
+    @property
+    def _sampler_state(self):
+        """The unguided DDIM state, under the name the benchmark reads after a run; no attribute before the first one."""
+        try:
+            return self.sampler_states[("ddim", False)]
+        except KeyError:
+            raise AttributeError("_sampler_state") from None
+
     def close(self):
-        """Releases the graphs (and the DDIM edit buffers) of the sampler states attached to this plan (ddim.py / plms.py /
-        dpm_solver.py fast paths)."""
-        for attr in ("_sampler_state", "_sampler_state_cfg", "_plms_state", "_plms_state_cfg", "_ddpm_state",
-                     "_dpm_state", "_dpm_state_cfg"):
-            st = self.__dict__.pop(attr, None)
-            if st is not None:
-                st.close()
+        """Drops every sampler state of the plan (sampler_states) and releases what each holds outside the plan's buffer
+        list: its captured graphs and the DDIM edit buffers."""
+        while self.sampler_states:
+            self.sampler_states.popitem()[1].close()
 
     def load_sampler_inputs(self, x, c_concat, c_cross, in_channels, rows_key, t_rows):
         """The per-call uploads of a sampler fast path: the latent (channels [0, C) of the stem input), the concat
@@ -604,49 +617,57 @@ class FidPlan(Emitter):
 
 # ====================================================================== sampler step graph
 class SamplerState:
-    """Device state of one DDIM run on a sampler-mode UNetPlan: latent x (fp32 NCHW),
-    pred_x0, the per-step coefficient / noise tables and the captured step graph
-    (UNet body -> upk_ddim_step_f32 -> upk_advance_step).
+    """Device state of one sampler's chain on a sampler-mode UNetPlan: latent x (fp32 NCHW), pred_x0, the per-step
+    coefficient / noise tables and the captured step graphs (UNet body -> the kind's step kernel, which also advances
+    the device-side step counter).  A plan keeps its states in UNetPlan.sampler_states (UNetPlan.sampler_state()).
 
-    DDIM edit mode (`edit`, set by the sampler before graph() / launch()): None = the plain generation graphs; "plain" =
-    upk_ddim_step_edit_f32 without a mask (chains that start inside the schedule: decode, a shortened `timesteps`);
-    "masked" = the same kernel with the keep table and the mask (inpainting).  Each has graphs of its own.  A chain
-    that starts at loop position k > 0 only presets plan.step to k: timestep rows and coefficients stay the S-row tables."""
+    kind: which step kernel a graph ends in, and `variant` (set_variant(), before graph() / launch()) which form of it the
+    next launches run; each variant has graphs of its own.
+      "ddim": plan rows = steps.  None = upk_ddim_step_f32 / _cfg_f32; "plain" = upk_ddim_step_edit_f32 without a mask
+              (chains that start inside the schedule: decode, a shortened `timesteps`); "masked" = the same kernel with the
+              keep table and the mask (inpainting).  A chain that starts at loop position k > 0 only presets plan.step to
+              k: timestep rows and coefficients stay the S-row tables.
+      "plms": one PLMS model evaluation, upk_plms_step_f32 (plan rows = evaluations = steps + 1; eps history `hist`).
+      "ddpm": one DDPM ancestral step, upk_ddpm_step_f32 (plan rows = timesteps of the chain, coefficient rows of 8, no
+              guidance); (flags, masked) = its DDPM_* flags and whether it blends q_sample(x0) under a mask.  The posterior
+              noise table [rows, n] is always there, and a masked chain adds the q_sample noise table, x0 and the expanded
+              mask: at B = 8, 32x24 and 1000 steps each table is 1000 * 24576 * 4 B = 98 MB.
+      "dpm":  one DPM-Solver++(2M) step, upk_dpmpp_2m_step_f32 (coefficient rows of 8); x0_old [n] is the data prediction of
+              the step before, which the kernel reads on second-order rows only, so nothing initialises it.
+    cfg: classifier-free guidance — the plan runs 2*B rows ([unconditional ; conditional], ddim.py:173-178), the latent
+    state has B = plan.B // 2 samples and the update combines the two halves of eps."""
 
-    def __init__(self, plan: UNetPlan, channels, cfg=False, plms=False, ddpm=False, dpm=False):
-        """cfg: classifier-free guidance — the plan runs 2*B rows ([unconditional ; conditional], ddim.py:173-178),
-        the latent state has B = plan.B // 2 samples and the update combines the two halves of eps.
-        plms: the graph is one PLMS model evaluation (upk_plms_step_f32; plan rows = evaluations = steps + 1).
-        ddpm: the graph is one DDPM ancestral step (upk_ddpm_step_f32; plan rows = timesteps of the chain, coefficient
-        rows of 8).  Its posterior noise table [rows, n] is always there, and a masked chain adds the q_sample noise
-        table, x0 and the expanded mask: at B = 8, 32x24 and 1000 steps each table is 1000 * 24576 * 4 B = 98 MB.
-        dpm: the graph is one DPM-Solver++(2M) step (upk_dpmpp_2m_step_f32; coefficient rows of 8, guidance allowed); x0_old
-        [n] is the data prediction of the step before, which the kernel reads on second-order rows only, so nothing
-        initialises it."""
+    def __init__(self, plan: UNetPlan, channels, kind="ddim", cfg=False):
         require(plan.mode == "sampler", "SamplerState needs a sampler-mode plan", ValueError)
-        self.plan = plan
-        self.cfg = bool(cfg)
-        self.plms = bool(plms)
+        require(kind in self._STEP, lambda: "SamplerState kind must be one of %s, got %r" % (tuple(self._STEP), kind), ValueError)
         require(not cfg or plan.B % 2 == 0, "guidance runs [uncond ; cond]: the plan's batch must be even", ValueError)
-        require(not (ddpm and (cfg or plms)), "the DDPM step has no guidance and no PLMS history", ValueError)
-        require(not (dpm and (plms or ddpm)), "the DPM-Solver++ step is a sampler state of its own", ValueError)
-        self.dpm = bool(dpm)
-        self.ddpm = bool(ddpm)
-        self.ddpm_flags, self.masked = 0, False  # (the DDPM variant the next graph() / step_eager() runs)
+        require(not (cfg and kind == "ddpm"), "the DDPM step has no guidance", ValueError)
+        self.plan = plan
+        self.kind = kind
+        self.cfg = bool(cfg)
         self.noise2 = self.x0 = self.mask = None
-        self.edit = None  # (the DDIM variant the next graph() runs: None / "plain" / "masked")
         self.keep = self.edit_mask = self.x_plain = None
         B, H, W, R = (plan.B // 2 if cfg else plan.B), plan.H, plan.W, plan.rows
         self.B = B
         self.C = channels
         self.x = plan.alloc(B, channels, H, W, dtype=torch.float32)
         self.pred_x0 = plan.alloc(B, channels, H, W, dtype=torch.float32)
-        self.coefs = plan.alloc(R, 8 if (ddpm or dpm) else 4, dtype=torch.float32)
+        self.coefs = plan.alloc(R, 8 if kind in ("ddpm", "dpm") else 4, dtype=torch.float32)
         self.noise = None
-        self.graphs = {}
+        self.graphs = {}  # (with_noise, scale, nsteps, variant) -> instantiated graph, least recently used first
         self.step_done = plan.alloc(1, dtype=torch.int32, zero=True)  # arrival counter of the step kernels
-        self.hist = plan.alloc(3, B * channels * H * W, dtype=torch.float32) if plms else None
-        self.x0_old = plan.alloc(B * channels * H * W, dtype=torch.float32) if dpm else None
+        self.hist = plan.alloc(3, B * channels * H * W, dtype=torch.float32) if kind == "plms" else None
+        self.x0_old = plan.alloc(B * channels * H * W, dtype=torch.float32) if kind == "dpm" else None
+        self.set_variant((0, False) if kind == "ddpm" else None)
+
+    def set_variant(self, variant):
+        """The variant of the launches that follow (class docstring); the one place that checks it against the kind."""
+        if self.kind == "ddpm":
+            ok = isinstance(variant, tuple) and len(variant) == 2 and isinstance(variant[0], int) and isinstance(variant[1], bool)
+        else:
+            ok = variant is None or (self.kind == "ddim" and variant in ("plain", "masked"))
+        require(ok, lambda: "a %r sampler state has no step variant %r" % (self.kind, variant), ValueError)
+        self.variant = variant
 
     def close(self):
         """Destroys the instantiated HIP graphs (they hold device memory; called when the owning plan is dropped).
@@ -685,81 +706,74 @@ class SamplerState:
             self.x_plain = torch.empty(self.B, self.C, p.H, p.W, dtype=torch.float32, device=p.dev)
         return self.keep, self.edit_mask, self.x_plain
 
+    # ---- the step of (kind, variant): the buffers it needs besides the noise table, and (kernel, the arguments between the
+    # context handle and the stream).  The arguments are read after the buffers exist.
+    def _ddim_step(self, nz, scale):
+        p, v = self.plan, self.variant
+        head = (self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(), nz)
+        if v is not None:
+            ptr = (lambda t: t.data_ptr()) if v == "masked" else (lambda t: None)
+            return p.lib.upk_ddim_step_edit_f32, head + (
+                ptr(self.keep), ptr(self.edit_mask), p.rows, p.step.data_ptr(), self.pred_x0.data_ptr(), ptr(self.x_plain),
+                p.xin.t.data_ptr(), p.xin.ld, self.B, self.C, p.H * p.W, float(scale), int(self.cfg))
+        tail = (p.step.data_ptr(), self.pred_x0.data_ptr(), p.xin.t.data_ptr(), p.xin.ld)
+        if self.cfg:
+            return p.lib.upk_ddim_step_cfg_f32, head + tail + (self.B, self.C, p.H * p.W, float(scale))
+        return p.lib.upk_ddim_step_f32, head + tail + (p.B, self.C, p.H * p.W)
+
+    def _plms_step(self, nz, scale):
+        p = self.plan
+        require(nz is None, "PLMS runs with eta = 0", ValueError)
+        return p.lib.upk_plms_step_f32, (
+            self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(), p.step.data_ptr(), self.hist.data_ptr(),
+            self.pred_x0.data_ptr(), p.xin.t.data_ptr(), p.xin.ld, self.B, self.C, p.H * p.W, float(scale), int(self.cfg))
+
+    def _ddpm_step(self, nz, scale):
+        p, (flags, masked) = self.plan, self.variant
+        ptr = (lambda t: t.data_ptr()) if masked else (lambda t: None)
+        return p.lib.upk_ddpm_step_f32, (
+            self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(), nz, ptr(self.noise2), ptr(self.x0), ptr(self.mask),
+            p.step.data_ptr(), self.pred_x0.data_ptr(), p.xin.t.data_ptr(), p.xin.ld, self.B, self.C, p.H * p.W, int(flags))
+
+    def _dpm_step(self, nz, scale):
+        p = self.plan
+        require(nz is None, "DPM-Solver++(2M) runs with eta = 0", ValueError)
+        return p.lib.upk_dpmpp_2m_step_f32, (
+            self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(), p.step.data_ptr(), self.x0_old.data_ptr(),
+            self.pred_x0.data_ptr(), p.xin.t.data_ptr(), p.xin.ld, self.B, self.C, p.H * p.W, 0, float(scale), int(self.cfg))
+
+    _STEP = {"ddim": _ddim_step, "plms": _plms_step, "ddpm": _ddpm_step, "dpm": _dpm_step}
+
+    def _ensure(self, with_noise):
+        """The buffers the step of (kind, variant) reads besides the state's own."""
+        if with_noise:
+            self.ensure_noise()
+        if self.kind == "ddpm" and self.variant[1]:
+            self.ensure_mask()
+        if self.kind == "ddim" and self.variant == "masked":
+            self.ensure_edit()
+
     def _emit_tail(self, stream, with_noise, scale=1.0):
         p = self.plan
-        nz = self.noise.data_ptr() if with_noise else None
+        fn, args = self._STEP[self.kind](self, self.noise.data_ptr() if with_noise else None, scale)
         # the step kernel also advances the device-side step counter (include/upk.h upk_step_autoadvance)
         p.ctx._chk(p.lib.upk_step_autoadvance(p.hctx, self.step_done.data_ptr()))
         try:
-            self._emit_step(stream, nz, scale)
+            p.ctx._chk(fn(p.hctx, *args, stream))
         finally:
             p.ctx._chk(p.lib.upk_step_autoadvance(p.hctx, None))
 
-    def _emit_step(self, stream, nz, scale):
-        p = self.plan
-        if self.ddpm:
-            m = self.masked
-            ptr = lambda t: t.data_ptr() if m else None
-            p.ctx._chk(p.lib.upk_ddpm_step_f32(p.hctx, self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(), nz,
-                                               ptr(self.noise2), ptr(self.x0), ptr(self.mask), p.step.data_ptr(),
-                                               self.pred_x0.data_ptr(), p.xin.t.data_ptr(), p.xin.ld, self.B, self.C,
-                                               p.H * p.W, int(self.ddpm_flags), stream))
-        elif self.dpm:
-            require(nz is None, "DPM-Solver++(2M) runs with eta = 0", ValueError)
-            p.ctx._chk(p.lib.upk_dpmpp_2m_step_f32(p.hctx, self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(),
-                                                   p.step.data_ptr(), self.x0_old.data_ptr(), self.pred_x0.data_ptr(),
-                                                   p.xin.t.data_ptr(), p.xin.ld, self.B, self.C, p.H * p.W, 0,
-                                                   float(scale), int(self.cfg), stream))
-        elif self.plms:
-            require(nz is None, "PLMS runs with eta = 0", ValueError)
-            p.ctx._chk(p.lib.upk_plms_step_f32(p.hctx, self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(),
-                                               p.step.data_ptr(), self.hist.data_ptr(), self.pred_x0.data_ptr(),
-                                               p.xin.t.data_ptr(), p.xin.ld, self.B, self.C, p.H * p.W, float(scale),
-                                               int(self.cfg), stream))
-        elif self.edit is not None:
-            m = self.edit == "masked"
-            ptr = lambda t: t.data_ptr() if m else None
-            p.ctx._chk(p.lib.upk_ddim_step_edit_f32(p.hctx, self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(), nz,
-                                                    ptr(self.keep), ptr(self.edit_mask), p.rows, p.step.data_ptr(),
-                                                    self.pred_x0.data_ptr(), ptr(self.x_plain), p.xin.t.data_ptr(),
-                                                    p.xin.ld, self.B, self.C, p.H * p.W, float(scale), int(self.cfg),
-                                                    stream))
-        elif self.cfg:
-            p.ctx._chk(p.lib.upk_ddim_step_cfg_f32(p.hctx, self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(), nz,
-                                                   p.step.data_ptr(), self.pred_x0.data_ptr(), p.xin.t.data_ptr(),
-                                                   p.xin.ld, self.B, self.C, p.H * p.W, float(scale), stream))
-        else:
-            p.ctx._chk(p.lib.upk_ddim_step_f32(p.hctx, self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(), nz,
-                                               p.step.data_ptr(), self.pred_x0.data_ptr(), p.xin.t.data_ptr(), p.xin.ld,
-                                               p.B, self.C, p.H * p.W, stream))
-
-    def step_eager(self, with_noise, scale=1.0):
-        s = self.plan.ctx._s()
-        self.plan.body.run(s)
-        self._emit_tail(s, with_noise, scale)
-
     def graph(self, with_noise, scale=1.0, nsteps=1):
-        """`nsteps` consecutive DDIM steps captured as ONE HIP graph (static shapes, device-side step index: the same
-        graph serves every position of the loop; the guidance scale is a kernel argument, so each scale value gets its
-        own graph).  nsteps > 1 saves the graph-to-graph launch gap of the steps inside."""
-        key = (with_noise, float(scale) if self.cfg else 1.0) + ((int(nsteps),) if nsteps != 1 else ())
-        if self.ddpm:
-            key += ("ddpm", int(self.ddpm_flags), bool(self.masked))
-        elif self.edit is not None:
-            require(self.edit in ("plain", "masked") and not (self.plms or self.dpm), "edit mode is 'plain' or 'masked', DDIM only",
-                    ValueError)
-            key += ("edit", self.edit)
+        """`nsteps` consecutive steps of the current variant captured as ONE HIP graph (static shapes, device-side step
+        index: the same graph serves every position of the loop; the guidance scale is a kernel argument, so each scale
+        value gets its own graph).  nsteps > 1 saves the graph-to-graph launch gap of the steps inside."""
+        key = (bool(with_noise), float(scale) if self.cfg else 1.0, int(nsteps), self.variant)
         g = self.graphs.pop(key, None)
         if g is not None:
             self.graphs[key] = g  # (most recently used last: eviction takes the least recently used graph)
         if g is None:
             p = self.plan
-            if with_noise:
-                self.ensure_noise()
-            if self.masked:
-                self.ensure_mask()
-            if self.edit == "masked":
-                self.ensure_edit()
+            self._ensure(with_noise)
             with L.host_io():  # (no other lane uploads from the host while this thread captures)
                 side = torch.cuda.Stream(device=p.dev)
                 side.wait_stream(torch.cuda.current_stream(p.dev))

@@ -4,18 +4,17 @@ linear multistep (Adams-Bashforth on eps) over the same schedule tables as DDIM 
 Fast path (same conditions as DDIMSampler's): ONE captured HIP graph = UNet body + upk_plms_step_f32 +
 upk_advance_step, replayed S + 1 times (the first step evaluates the model twice); the eps history ring,
 the Adams-Bashforth combination and classifier-free guidance live in the update kernel, the timestep
-embeddings of all evaluations are precomputed like DDIM's.  Anything else (masks, score correctors, noise
-dropout) runs on the general path: one UNetModel.forward per model evaluation driven from Python.
+embeddings of all evaluations are precomputed like DDIM's.  The launches go through chain.run like the other samplers'
+(engine.SamplerState kind "plms"), one evaluation per launch: PLMS steps are not grouped.  Anything else (masks, score
+correctors, noise dropout) runs on the general path: one UNetModel.forward per model evaluation driven from Python.
 """
-import contextlib
-
 import numpy as np
 import torch
 
-from . import rng
-from .ddim import DDIMSampler
+from . import chain, rng
 from ._check import require
-from ._lib import host_io
+from .ddim import DDIMSampler
+from .schedule import ddim_coefficient_table
 
 # Adams-Bashforth weights on [e_t, e_{t-1}, e_{t-2}, e_{t-3}] by available history (plms.py:224-234)
 _AB = {1: (3 / 2, -1 / 2), 2: (23 / 12, -16 / 12, 5 / 12), 3: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}
@@ -37,12 +36,8 @@ class PLMSSampler(DDIMSampler):
         draws the reference makes and discards are not made."""
         noise_keys = kwargs.get("noise_keys")
         rng.check_keys(noise_keys, batch_size, normals_sequence)
-        acp = self.model.alphas_cumprod  # (tables of an unchanged (S, eta) are kept between calls, as in DDIMSampler.sample)
-        key = (int(S), float(eta), id(self.model), acp.data_ptr(), int(getattr(acp, "_version", 0)), str(acp.device))
-        if verbose or getattr(self, "_sched_key", None) != key:
-            with host_io():
-                self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
-            self._sched_key = key
+        self._ensure_schedule((int(S), float(eta)), lambda: self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose),
+                              verbose)
         C, H, W = shape
         size = (batch_size, C, H, W)
         print(f"Data shape for PLMS sampling is {size}")
@@ -63,20 +58,13 @@ class PLMSSampler(DDIMSampler):
             raise NotImplementedError("PLMS with the original 1000 steps / quantized x0 is not on the UPGPT path")
         device = self.model.betas.device
         b = shape[0]
-        if timesteps is None:
-            timesteps = self.ddim_timesteps
-        else:
-            subset_end = int(min(timesteps / self.ddim_timesteps.shape[0], 1) * self.ddim_timesteps.shape[0]) - 1
-            timesteps = self.ddim_timesteps[:subset_end]
+        timesteps = self._subset(timesteps)
         if self._fast_ok(cond, ddim_use_original_steps, quantize_denoised, mask, noise_dropout, score_corrector,
                          unconditional_guidance_scale, unconditional_conditioning) \
                 and len(timesteps) == len(self.ddim_timesteps) and temperature == 1.:
             return self._fast_plms(cond, shape, x_T, timesteps, callback, img_callback, log_every_t,
                                    unconditional_guidance_scale, unconditional_conditioning, noise_keys)
-        if x_T is not None:
-            img = x_T.to(device)
-        else:
-            img = torch.randn(shape, device=device) if noise_keys is None else rng.randn(noise_keys, shape, rng.STREAM_XT)
+        img = chain.start_latent(x_T, noise_keys, shape, device)
         intermediates = {"x_inter": [img], "pred_x0": [img]}
         time_range = np.flip(timesteps)
         total = timesteps.shape[0]
@@ -108,8 +96,6 @@ class PLMSSampler(DDIMSampler):
 
     def _fast_plms(self, cond, shape, x_T, timesteps, callback, img_callback, log_every_t, cfg_scale, uc,
                    noise_keys=None):
-        from .ddim import ddim_coefficient_table
-        from .engine import SamplerState
         model = self.model
         unet = model.model.diffusion_model
         b, C, H, W = shape
@@ -121,11 +107,7 @@ class PLMSSampler(DDIMSampler):
         plan = unet.plan(2 * b if cfg else b, H, W, c_cross.shape[1], S + 1, "sampler")  # rows = model evaluations
         dev = plan.dev
         with torch.cuda.device(dev):
-            attr = "_plms_state_cfg" if cfg else "_plms_state"
-            st = getattr(plan, attr, None)
-            if st is None:
-                st = SamplerState(plan, C, cfg=cfg, plms=True)
-                setattr(plan, attr, st)
+            st = plan.sampler_state("plms", C, cfg)
             order = np.arange(S)[::-1].copy()
             t_desc = np.asarray(timesteps)[order].astype(np.float32)
             # evaluation k runs at: t_0, then (x~, t_next = t_1) for the Euler corrector, then t_1, t_2, ...
@@ -137,21 +119,11 @@ class PLMSSampler(DDIMSampler):
             fresh_rows = getattr(plan, "_t_rows_key", None) != rkey
             fresh_coefs = getattr(st, "_coef_key", None) != ckey
             fresh = fresh_rows or fresh_coefs
-            on_host = any(t is not None and torch.is_tensor(t) and not t.is_cuda for t in (x_T, c_concat, c_cross))
-            with (host_io() if (fresh or on_host) else contextlib.nullcontext()):  # (ddim.py _fast_sampling: same rule)
-                if x_T is not None:
-                    img = x_T.to(dev, torch.float32)
-                else:
-                    img = torch.randn(shape, device=dev) if noise_keys is None else rng.randn(noise_keys, shape, rng.STREAM_XT)
-                st.x.copy_(img)
-                plan.load_x_nchw(torch.cat([st.x, st.x]) if cfg else st.x, 0, 0)
-                if c_concat is not None:
-                    plan.load_x_nchw(c_concat, C, plan.cin_pad)
-                require(C + (0 if c_concat is None else c_concat.shape[1]) == unet.in_channels, "latent + concat channels != UNet in_channels", ValueError)
-                plan.load_context(c_cross)
-                if fresh_rows:
-                    plan.t_rows.copy_(torch.as_tensor(t_eval))
-                    plan._t_rows_key = rkey
+            on_host = chain.on_host(x_T, c_concat, c_cross)
+            with chain.upload_lock(fresh or on_host):
+                st.x.copy_(chain.start_latent(x_T, noise_keys, shape, dev, torch.float32))
+                plan.load_sampler_inputs(torch.cat([st.x, st.x]) if cfg else st.x, c_concat, c_cross, unet.in_channels,
+                                         rkey, t_eval)
                 if fresh_coefs:
                     st.coefs[:S].copy_(ddim_coefficient_table(self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sigmas,
                                                               self.ddim_sqrt_one_minus_alphas, order))
@@ -162,17 +134,16 @@ class PLMSSampler(DDIMSampler):
                 plan.prep.run()
             intermediates = {"x_inter": [st.x.clone()], "pred_x0": [st.x.clone()]}
             print(f"Running PLMS Sampling with {S} timesteps")
-            for k in range(S + 1):
-                st.launch(False, cfg_scale)
-                if k == 0:
-                    continue  # predictor evaluation of the first step
-                i = k - 1
-                index = S - i - 1
+            # one model evaluation per graph launch: S + 1 launches from position -1, the predictor evaluation of the first step
+            logged = chain.logged_at(S, log_every_t)
+            for i in chain.run(st, S + 1, 1, True, logged, False, cfg_scale, first=-1):
+                if i < 0:
+                    continue
                 if callback:
                     callback(i)
                 if img_callback:
                     img_callback(st.pred_x0.clone(), i)
-                if index % log_every_t == 0 or index == S - 1:
+                if logged(i):
                     intermediates["x_inter"].append(st.x.clone())
                     intermediates["pred_x0"].append(st.pred_x0.clone())
             return st.x.clone(), intermediates
@@ -182,16 +153,8 @@ class PLMSSampler(DDIMSampler):
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, old_eps=None, t_next=None):
         def model_eps(xx, tt):
-            if unconditional_conditioning is None or unconditional_guidance_scale == 1.:
-                e = self.model.apply_model(xx, tt, c)
-            else:
-                e_u, e = self.model.apply_model(torch.cat([xx] * 2), torch.cat([tt] * 2),
-                                                self._cat_cond(unconditional_conditioning, c)).chunk(2)
-                e = e_u + unconditional_guidance_scale * (e - e_u)
-            if score_corrector is not None:
-                require(self.model.parameterization == "eps", "classifier-free guidance / score correction needs an eps-parameterised model", NotImplementedError)
-                e = score_corrector.modify_score(self.model, e, xx, tt, c, **corrector_kwargs)
-            return e
+            return self._guided_eps(xx, tt, c, unconditional_guidance_scale, unconditional_conditioning, score_corrector,
+                                    corrector_kwargs)
 
         def update(e):  # the DDIM update with sigma = 0 (eta is forced to 0), fused kernel
             return self._ddim_update(x, e, index, temperature=temperature, noise_dropout=noise_dropout,
