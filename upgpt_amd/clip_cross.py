@@ -17,15 +17,15 @@ a `CrossAttention(768, 768, heads=8, dim_head=96)`:
   `upk_attention_fewkeys_f16` (8 heads of 96 over n <= 16 keys, k and v two column slices of that GEMM's output), and
   the `to_out` GEMM with its bias into fp32.  No torch op computes anything and nothing visits the host in between.
 """
-import os
-
 import torch
 from torch import nn
 
+from . import knobs as K
 from .clip_image import CLIPVisionHF
 from .clip_text import CLIPTextTransformer
 from .engine import Act, Emitter, Packer, Program
 from .params import ParamTree, weights_fingerprint
+from .plancache import PlanCache
 
 LAION_L14 = "laion/CLIP-ViT-L-14-laion2B-s32B-b82K"
 MAX_STYLES = 16  # keys of upk_attention_fewkeys_f16
@@ -82,7 +82,7 @@ class _CrossPlan(Emitter):
         self.out = self.alloc(x.M, get("to_out.0.weight").shape[0], dtype=torch.float32)
         self.conv(P, att, pk.pack("to_out.0"), out_f32=self.out)
         self.shape = (B, S, self.out.shape[1])
-        self.apply_tuning(tune_missing=os.environ.get("UPGPT_AUTOTUNE", "0") == "1")
+        self.apply_tuning(tune_missing=K.autotune_missing())
 
 
 class CLIPTextImageCrossAtten(nn.Module):
@@ -118,7 +118,7 @@ class CLIPTextImageCrossAtten(nn.Module):
         self.cross_att = ParamTree({"to_q.weight": (inner, width), "to_k.weight": (inner, width),
                                     "to_v.weight": (inner, width), "to_out.0.weight": (width, inner),
                                     "to_out.0.bias": (width,)})
-        self._plans, self._fp = {}, None
+        self._plans, self._fp = PlanCache(2), None
 
     def freeze(self):
         """modules.py:320-323: the CLIP model is frozen, the cross-attention stays trainable."""
@@ -170,26 +170,23 @@ class CLIPTextImageCrossAtten(nn.Module):
 
     # ---- the stage
     def _plan(self, B, n):
-        from ._lib import PLAN_LOCK, concurrency, current_lane, get_context, host_io
+        from ._lib import PLAN_LOCK, get_context
         text_plan, image_plan = self.model.text_tower._plan(B), self.model.vision_tower._plan(B * n)
         p = self.cross_att.to_q.weight
         with PLAN_LOCK:
             fp = weights_fingerprint(self.cross_att)
             if fp != self._fp:
-                self._plans, self._fp = {}, fp
-            key = (B, n, concurrency() > 1, current_lane())
-            ent = self._plans.get(key)
-            if ent is None or ent[0] is not text_plan or ent[1] is not image_plan:  # (a tower rebuilt or evicted its plan)
-                mine = [k for k in self._plans if k[-1] == key[-1] and k != key]
-                if len(mine) >= 2:
-                    self._plans.pop(mine[0])
+                self._plans.drop(device=p.device)
+                self._fp = fp
+
+            def build():
                 params = dict(self.cross_att.named_parameters())
-                with torch.cuda.device(p.device), host_io():
-                    plan = _CrossPlan(get_context(p.device), lambda name: params[name].data, text_plan, image_plan, B, n,
-                                      self.heads, self.dim_head)
-                    torch.cuda.current_stream(p.device).synchronize()  # (weights packed on this lane's stream)
-                ent = self._plans[key] = (text_plan, image_plan, plan)
-        return ent
+                plan = _CrossPlan(get_context(p.device), lambda name: params[name].data, text_plan, image_plan, B, n,
+                                  self.heads, self.dim_head)
+                torch.cuda.current_stream(p.device).synchronize()  # (weights packed on this lane's stream)
+                return text_plan, image_plan, plan
+            # (not valid: a tower rebuilt or evicted its plan)
+            return self._plans.get((B, n), build, p.device, lambda e: e[0] is text_plan and e[1] is image_plan)
 
     def forward(self, txt, styles, use_text_style=False):
         if self.style_encode is None:

@@ -15,16 +15,16 @@ bias=False) patch embedding -> [class token ; 256 patches] + positional embeddin
   LayerNorm folded into the q|k|v projection and into c_fc (`upk_conv_desc.ln_colsum`), `upk_attention_f16`,
   `UPK_F_QUICKGELU`, residual epilogues; the final projection is a GEMM over the class-token rows.
 """
-import os
-
 import torch
 from torch import nn
 
 from . import _lib as L
+from . import knobs as K
 from .clip_text import hidden_act
 from .engine import Act, Emitter, PW, Packer, Program, _rup
 from .packing import SharedPacks
 from .params import ParamTree, weights_fingerprint
+from .plancache import PlanCache
 
 CLIP_L14_VISION = dict(width=1024, layers=24, heads=16, patch_size=14, image_size=224, output_dim=768, eps=1e-5,
                        hidden_act="quick_gelu")
@@ -153,7 +153,7 @@ class _VisualPlan(Emitter):
         self.out = self.alloc(N, cfg["output_dim"], dtype=torch.float32)
         self.conv(P, cls_rows, pk.pack("proj_t", bias=False), out_f32=self.out)
         self.out16 = None
-        self.apply_tuning(tune_missing=os.environ.get("UPGPT_AUTOTUNE", "0") == "1")
+        self.apply_tuning(tune_missing=K.autotune_missing())
 
     def _ln(self, P, x, gamma, beta, eps, y, rows, ldx=None):
         fn, h, chk = self.lib.upk_layernorm_f16, self.hctx, self._chk
@@ -197,7 +197,7 @@ class _VisionTower(ParamTree):
         super().__init__()
         self.config = config
         self.add_params(shapes)
-        self._plans = {}
+        self._plans = PlanCache(2)
         self._fp = None
 
     def _plan(self, N):
@@ -206,24 +206,20 @@ class _VisionTower(ParamTree):
         if p.device.type != "cuda":
             raise RuntimeError("upgpt_amd.%s computes only through the HIP kernels on an MI355X: move it to 'cuda' "
                                "first. There is no CPU fallback." % type(self).__name__)
-        from ._lib import PLAN_LOCK, concurrency, current_lane, get_context, host_io
-        with PLAN_LOCK:  # (execution lanes: a plan — buffers and packed weights — per (crop count, tuning table, lane))
+        with L.PLAN_LOCK:  # (execution lanes: a plan — buffers and packed weights — per (crop count, tuning table, lane))
             fp = weights_fingerprint(self)
             if fp != self._fp:
-                self._plans, self._fp, self._packs = {}, fp, SharedPacks()
-            key = (N, concurrency() > 1, current_lane())
-            plan = self._plans.get(key)
-            if plan is None:
-                mine = [k for k in self._plans if k[-1] == key[-1]]
-                if len(mine) >= 2:
-                    self._plans.pop(mine[0])
+                self._plans.drop(device=p.device)
+                self._fp, self._packs = fp, SharedPacks()
+
+            def build():
                 params = dict(self.named_parameters())
-                with torch.cuda.device(p.device), host_io():
-                    plan = self._plans[key] = _VisualPlan(get_context(p.device), self.config, lambda n: params[n].data, N,
-                                                          shared=self._packs, names=self.NAMES)
-                    if self._packs.take_fresh():
-                        torch.cuda.current_stream(p.device).synchronize()  # (packed on this lane's stream, read from every lane's)
-        return plan
+                plan = _VisualPlan(L.get_context(p.device), self.config, lambda n: params[n].data, N,
+                                   shared=self._packs, names=self.NAMES)
+                if self._packs.take_fresh():
+                    torch.cuda.current_stream(p.device).synchronize()  # (packed on this lane's stream, read from every lane's)
+                return plan
+            return self._plans.get((N,), build, p.device)
 
     def forward(self, images):
         plan = self._plan(int(images.shape[0]))

@@ -20,15 +20,15 @@ MLP 768 -> 3072 -> 768 with quick_gelu) -> final LayerNorm; the embedder returns
   available offline: `encode(text)` needs `transformers.CLIPTokenizer` files on disk, `encode_tokens(ids)` takes the
   int token ids directly (the oracle boundary for this stage).
 """
-import os
-
 import torch
 from torch import nn
 
 from . import _lib as L
+from . import knobs as K
 from .engine import Act, Emitter, Packer, Program, _rup
 from .packing import SharedPacks
 from .params import ParamTree, weights_fingerprint
+from .plancache import PlanCache
 
 # openai/clip-vit-large-patch14 text tower (config.json of the hub model; CLIPTextConfig)
 CLIP_L14_TEXT = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12,
@@ -164,7 +164,7 @@ class _TextPlan(Emitter):
             self.out = Act(self.alloc(M, d), B, S, 1, d)
             al = (x.t.data_ptr(), x.ld, M, d, g.data_ptr(), b_.data_ptr(), eps, self.out.t.data_ptr(), self.out.ld)
             P.add(lambda s: chk(fn_l(h, *al, s)), x, g, b_, self.out, cls="layernorm")
-        self.apply_tuning(tune_missing=os.environ.get("UPGPT_AUTOTUNE", "0") == "1")
+        self.apply_tuning(tune_missing=K.autotune_missing())
 
     def run(self, ids):
         self.check(ids)
@@ -203,7 +203,7 @@ class _TextTower(ParamTree):
         super().__init__()
         self.config = config
         self.add_params(shapes)
-        self._plans = {}
+        self._plans = PlanCache(4)
         self._fp = None
 
     def _plan(self, B):
@@ -212,24 +212,20 @@ class _TextTower(ParamTree):
         if p.device.type != "cuda":
             raise RuntimeError("upgpt_amd.%s computes only through the HIP kernels on an MI355X: move it to 'cuda' first. "
                                "There is no CPU fallback." % type(self).__name__)
-        from ._lib import PLAN_LOCK, concurrency, current_lane, get_context, host_io
-        with PLAN_LOCK:  # (execution lanes: a plan — buffers and packed weights — per (batch, tuning table, lane))
+        with L.PLAN_LOCK:  # (execution lanes: a plan — buffers and packed weights — per (batch, tuning table, lane))
             fp = weights_fingerprint(self)
             if fp != self._fp:
-                self._plans, self._fp, self._packs = {}, fp, SharedPacks()
-            key = (B, concurrency() > 1, current_lane())
-            plan = self._plans.get(key)
-            if plan is None:
-                mine = [k for k in self._plans if k[-1] == key[-1]]
-                if len(mine) >= 4:
-                    self._plans.pop(mine[0])
+                self._plans.drop(device=p.device)
+                self._fp, self._packs = fp, SharedPacks()
+
+            def build():
                 params = dict(self.named_parameters())
-                with torch.cuda.device(p.device), host_io():
-                    plan = self._plans[key] = _TextPlan(get_context(p.device), self.config, lambda n: params[n].data, B,
-                                                        names=self.NAMES, shared=self._packs)
-                    if self._packs.take_fresh():
-                        torch.cuda.current_stream(p.device).synchronize()
-        return plan
+                plan = _TextPlan(L.get_context(p.device), self.config, lambda n: params[n].data, B, names=self.NAMES,
+                                 shared=self._packs)
+                if self._packs.take_fresh():
+                    torch.cuda.current_stream(p.device).synchronize()  # (packed on this lane's stream, read from every lane's)
+                return plan
+            return self._plans.get((B,), build, p.device)
 
     def _run(self, input_ids):
         plan = self._plan(int(input_ids.shape[0]))

@@ -88,7 +88,7 @@ class Emitter:
         overlay = None
         if cache is None:
             cache = TUNE_CACHE
-            if L.concurrency() > 1 and os.environ.get("UPGPT_LANES_TUNING", "1") == "1":
+            if L.concurrency() > 1 and K.lanes_tuning():
                 overlay = TUNE_CACHE_LANES  # (several batches in flight: the throughput-tuned choices come first)
                 overlay.bind(self.lib)
         cache.bind(self.lib)
@@ -512,7 +512,7 @@ class Emitter:
         # the streaming form): either one keeps the launch fused and goes before "__unfuse_mlp_M__", which
         # stays the answer for the resident form and wherever the stored height is outside the kernel's domain
         rows = self.row_chain_rows("mlp", M, 0)
-        if (not rows and K.MLP_FUSE == "auto" and L.concurrency() > 1 and os.environ.get("UPGPT_LANES_TUNING", "1") == "1"
+        if (not rows and K.MLP_FUSE == "auto" and L.concurrency() > 1 and K.lanes_tuning()
                 and M in TUNE_CACHE_LANES.meta.get("__unfuse_mlp_M__", ())):
             # several batches in flight: the kernel holds every CU with one register-heavy workgroup that streams both
             # weights (21 us of chip time per launch); GEGLU + (ff.net.2 o proj_out) as two launches on tiles tuned for a
@@ -557,7 +557,7 @@ class Emitter:
         forced = K.MLP_ROWS if kind == "mlp" else (K.HB_ROWS if kind == "hblock" else 0) or K.XB_ROWS
         if forced:
             return forced
-        if L.concurrency() > 1 and os.environ.get("UPGPT_LANES_TUNING", "1") == "1":
+        if L.concurrency() > 1 and K.lanes_tuning():
             tab = (TUNE_CACHE_LANES.meta.get("__mlp_rows__", {}) if kind == "mlp"
                    else TUNE_CACHE_LANES.meta.get("__row_chain_rows__", {}).get(kind, {}))
             r = tab.get(str(M))

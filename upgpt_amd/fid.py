@@ -15,6 +15,7 @@ from . import _lib
 from ._check import require
 from .packing import BN_LEAVES, FID_DIMS, inception_units
 from .params import ParamTree, weights_fingerprint
+from .plancache import PlanCache
 
 RESIZE = 299
 MIN_SIDE = 75  # without resizing: the smallest input that leaves a pixel after Mixed_7a
@@ -48,7 +49,7 @@ class FIDInception(ParamTree):
         require(int(pictures_per_pass) >= 1, "pictures_per_pass must be positive", ValueError)
         self.pictures_per_pass = int(pictures_per_pass)
         self._packed = None
-        self._plans = {}
+        self._plans = PlanCache(4, tuned=False)
 
     @classmethod
     def from_file(cls, path, pictures_per_pass=32):
@@ -77,15 +78,9 @@ class FIDInception(ParamTree):
                 with torch.cuda.device(p.device), _lib.host_io():
                     self._packed = (fp, PackedInception(ctx, lambda n: tensors[n].data))
                     torch.cuda.current_stream(p.device).synchronize()  # (packed on this lane's stream, read from every lane's)
-                self._plans = {}
-            key = (pictures, H, W, bool(resize), _lib.current_lane())
-            if key not in self._plans:
-                mine = [k for k in self._plans if k[-1] == key[-1]]
-                if len(mine) >= 4:  # (per lane: another lane's plans may be executing)
-                    self._plans.pop(mine[0])
-                with torch.cuda.device(p.device), _lib.host_io():
-                    self._plans[key] = FidPlan(ctx, self._packed[1], pictures, H, W, resize)
-            return self._plans[key]
+                self._plans.drop(device=p.device)
+            return self._plans.get((pictures, H, W, bool(resize)),
+                                   lambda: FidPlan(ctx, self._packed[1], pictures, H, W, resize), p.device)
 
     def _features(self, name, x, n, h, w, f32, resize, normalize):
         p = next(self.parameters())

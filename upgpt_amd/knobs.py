@@ -1,4 +1,5 @@
-"""Environment switches of the lowering (read at import; tests and tuning scripts flip the attributes of THIS module)."""
+"""Environment switches of the lowering (read at import; tests and tuning scripts flip the attributes of THIS module).
+The two functions at the end read the environment when called: tests flip it between two plans of one process."""
 import os
 
 # GroupNorm statistics of the VAE decoder's tensors as conv by-products (gn_stats_cap + upk_groupnorm_finalize_f32):
@@ -40,4 +41,16 @@ HBLOCK_GN = os.environ.get("UPGPT_HBLOCK_GN", "1") == "1"  # SpatialTransformer.
 WEIGHT_PREFETCH = os.environ.get("UPGPT_WEIGHT_PREFETCH", "auto")
 WEIGHT_PREFETCH_AHEAD = int(os.environ.get("UPGPT_WEIGHT_PREFETCH_AHEAD", "1"))  # which following launch's weight: 1 = the next
 WEIGHT_PREFETCH_MAX = int(os.environ.get("UPGPT_WEIGHT_PREFETCH_MAX", str(32 << 20)))  # bytes of the next weight at most
+
+
+def autotune_missing():
+    """UPGPT_AUTOTUNE=1: shapes outside the tuning table are timed on the device when a plan is built (apply_tuning)."""
+    return os.environ.get("UPGPT_AUTOTUNE", "0") == "1"
+
+
+def lanes_tuning():
+    """UPGPT_LANES_TUNING=0: plans for several batches in flight keep the single-forward table and its decisions."""
+    return os.environ.get("UPGPT_LANES_TUNING", "1") == "1"
+
+
 LN_LAUNCH_US = 5.0  # what a separate LayerNorm launch costs inside the replayed forward (3.8 us of kernel + its boundary: DESIGN.md 11i / 11j)

@@ -17,6 +17,7 @@ from . import _lib
 from ._check import require
 from .packing import VGG16_TAP_CHANNELS, vgg16_convs
 from .params import ParamNode, ParamTree, weights_fingerprint
+from .plancache import PlanCache
 
 SHIFT = (-.030, -.088, -.188)
 SCALE = (.458, .448, .450)
@@ -67,7 +68,7 @@ class LPIPS(ParamTree):
         node.register_buffer("scale", torch.tensor(SCALE, dtype=torch.float32).view(1, 3, 1, 1))
         self.add_module("scaling_layer", node)
         self._packed = None
-        self._plans = {}
+        self._plans = PlanCache(4, tuned=False)
 
     @classmethod
     def from_files(cls, vgg16_path, lin_path, pairs_per_pass=16):
@@ -108,15 +109,8 @@ class LPIPS(ParamTree):
                 with torch.cuda.device(p.device), _lib.host_io():
                     self._packed = (fp, PackedVGG16(ctx, lambda n: tensors[n].data))
                     torch.cuda.current_stream(p.device).synchronize()  # (packed on this lane's stream, read from every lane's)
-                self._plans = {}
-            key = (pairs, H, W, _lib.current_lane())
-            if key not in self._plans:
-                mine = [k for k in self._plans if k[-1] == key[-1]]
-                if len(mine) >= 4:  # (per lane: another lane's plans may be executing)
-                    self._plans.pop(mine[0])
-                with torch.cuda.device(p.device), _lib.host_io():
-                    self._plans[key] = LpipsPlan(ctx, self._packed[1], pairs, H, W)
-            return self._plans[key]
+                self._plans.drop(device=p.device)
+            return self._plans.get((pairs, H, W), lambda: LpipsPlan(ctx, self._packed[1], pairs, H, W), p.device)
 
     def _layers(self, name, a, b, n, h, w, f32, normalize):
         """[n, 5] fp32: a, b as _check_pictures / forward validated them."""

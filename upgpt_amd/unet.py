@@ -3,13 +3,14 @@
 hand-written HIP kernels of libupk.so.  Weights live in a ParamTree with the reference's
 state-dict keys (time_embed.0.weight, input_blocks.1.1.transformer_blocks.0.attn2.to_k.weight,
 out.2.weight, ...)."""
-import os
 import threading
 
 import torch
 
 from .arch import UNetArch
+from .knobs import autotune_missing
 from .params import ParamTree, weights_fingerprint
+from .plancache import PlanCache
 from ._check import require
 
 # thread -> {id(unet): selection}: a module-level object, so that a model still copies and pickles
@@ -35,7 +36,7 @@ class UNetModel(ParamTree):
         self.predict_codebook_ids = False
         self.add_params(a.param_shapes())
         self._packed = {}     # tag -> (fingerprint, PackedUNet)
-        self._plans = {}      # (tag, B, H, W, n_ctx, rows, mode, several batches in flight, lane) -> UNetPlan
+        self._plans = PlanCache(8)  # head (tag, B, H, W, n_ctx, rows, mode) -> UNetPlan (DESIGN.md "Plan caches")
         self._weight_override = None  # (tag, callable name -> tensor): EMA weights without copying
 
     # ---- engine plumbing
@@ -71,66 +72,45 @@ class UNetModel(ParamTree):
         return None if sel == "live" else sel
 
     def packed(self):
-        from ._lib import PLAN_LOCK
-        with PLAN_LOCK:
-            return self._packed_locked()
-
-    def _packed_locked(self):
-        from ._lib import get_context
+        from ._lib import PLAN_LOCK, get_context, host_io
         from .engine import PackedUNet
         dev = self._device()
-        ctx = get_context(dev)
-        sel = self._weight_selection()
-        if sel is None:
-            tag, fp = "live", weights_fingerprint(self)
-            params = dict(self.named_parameters())
-            get = lambda n: params[n].data
-        else:
-            tag, get, fpf = sel
-            fp = fpf()
-        ent = self._packed.get(tag)
-        if ent is None or ent[0] != fp:
-            from ._lib import host_io
-            with torch.cuda.device(dev), host_io():
-                pk = PackedUNet(ctx, self.arch, get)
-                # the pack kernels ran on THIS thread's stream; other lanes read the packed weights from theirs
-                torch.cuda.current_stream(dev).synchronize()
-            self._packed[tag] = (fp, pk)
-            stale = [k for k in self._plans if k[0] == tag]
-            if stale:
-                torch.cuda.synchronize(dev)  # (another lane may still be replaying graphs of the old weight set)
-            for k in stale:
-                self._plans.pop(k).close()  # (plans of the old weight set: their captured graphs go with them)
-        return ctx, tag, self._packed[tag][1]
+        with PLAN_LOCK:
+            ctx = get_context(dev)
+            sel = self._weight_selection()
+            if sel is None:
+                tag, fp = "live", weights_fingerprint(self)
+                params = dict(self.named_parameters())
+                get = lambda n: params[n].data
+            else:
+                tag, get, fpf = sel
+                fp = fpf()
+            ent = self._packed.get(tag)
+            if ent is None or ent[0] != fp:
+                with torch.cuda.device(dev), host_io():
+                    pk = PackedUNet(ctx, self.arch, get)
+                    # the pack kernels ran on THIS thread's stream; other lanes read the packed weights from theirs
+                    torch.cuda.current_stream(dev).synchronize()
+                self._packed[tag] = (fp, pk)
+                self._plans.drop(lambda k: k[0] == tag, dev)  # (plans of the old weight set: their captured graphs go with them)
+            return ctx, tag, self._packed[tag][1]
 
     def plan(self, B, H, W, n_ctx, rows, mode):
         from ._lib import PLAN_LOCK
-        with PLAN_LOCK:
-            return self._plan_locked(B, H, W, n_ctx, rows, mode)
-
-    def _plan_locked(self, B, H, W, n_ctx, rows, mode):
-        from ._lib import concurrency, current_lane
         from .engine import UNetPlan
-        ctx, tag, pk = self.packed()  # (ctx = the calling thread's lane: own workspace, own buffers; weights shared)
-        key = (tag, B, H, W, n_ctx, rows, mode, concurrency() > 1, current_lane())
-        pl = self._plans.get(key)
-        if pl is None:
-            mine = [k for k in self._plans if k[-1] == key[-1]]
-            if len(mine) >= 8:  # bound device memory held by stale shapes — per lane: another lane's plans may be executing
-                self._plans.pop(mine[0]).close()
-            from ._lib import host_io
-            with torch.cuda.device(ctx.device), host_io():  # (descriptor tables are uploaded from the host)
+        with PLAN_LOCK:
+            ctx, tag, pk = self.packed()  # (ctx = the calling thread's lane: own workspace, own buffers; weights shared)
+
+            def build():
                 pl = UNetPlan(ctx, pk, B, H, W, n_ctx, rows, mode)
-                pl.apply_tuning(tune_missing=os.environ.get("UPGPT_AUTOTUNE", "0") == "1")
-            self._plans[key] = pl
-        return pl
+                pl.apply_tuning(tune_missing=autotune_missing())
+                return pl
+            return self._plans.get((tag, B, H, W, n_ctx, rows, mode), build, ctx.device)
 
     def invalidate(self):
         """Drops the packed weights and every plan (call after editing parameters through `.data`)."""
         self._packed.clear()
-        for pl in self._plans.values():
-            pl.close()
-        self._plans.clear()
+        self._plans.drop(device=next(self.parameters()).device)
 
     # ---- reference surface
     def convert_to_fp16(self):

@@ -2,13 +2,13 @@
 encode 324-328, decode 330-333) with the Encoder / Decoder (model.py:368-568) running on
 libupk.so: decode is on the images/sec path, encode is the first "next" row of SURVEY.md
 §8f (reconstruction output of log_images, img2img entry)."""
-import os
-
 import torch
 
 from .arch import VAEArch
 from .config import instantiate_from_config
+from .knobs import autotune_missing
 from .params import ParamTree, weights_fingerprint
+from .plancache import PlanCache
 from ._check import require
 from ._lib import host_io
 
@@ -64,9 +64,9 @@ class AutoencoderKL(ParamTree):
         if monitor is not None:
             self.monitor = monitor
         self._packed = None
-        self._plans = {}
+        self._plans = PlanCache(4)
         self._packed_enc = None
-        self._enc_plans = {}
+        self._enc_plans = PlanCache(4)
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
 
@@ -79,37 +79,35 @@ class AutoencoderKL(ParamTree):
         self.load_state_dict(sd, strict=False)
         print(f"Restored from {path}")
 
-    def _decode_plan(self, B, h, w, scale_factor):
-        from ._lib import PLAN_LOCK
-        with PLAN_LOCK:
-            return self._decode_plan_locked(B, h, w, scale_factor)
-
-    def _decode_plan_locked(self, B, h, w, scale_factor):
-        from ._lib import get_context
-        from .engine import PackedVAEDecoder, VAEDecodePlan
+    def _half_plan(self, half, packed_at, plans, Packed, Plan, head):
+        """The calling lane's plan of one half (decode / encode) for `head`, the half's weights packed on first use."""
+        from ._lib import PLAN_LOCK, get_context
         p = next(self.parameters())
         if p.device.type != "cuda":
-            raise RuntimeError("upgpt_amd.AutoencoderKL.decode runs only on the MI355X HIP path (parameters are on "
-                               "%s); there is no CPU fallback" % p.device)
-        ctx = get_context(p.device)
-        fp = weights_fingerprint(self)
-        if self._packed is None or self._packed[0] != fp:
-            params = dict(self.named_parameters())
-            with torch.cuda.device(p.device), host_io():
-                self._packed = (fp, PackedVAEDecoder(ctx, self.arch, lambda n: params[n].data))
-                torch.cuda.current_stream(p.device).synchronize()  # (packed on this lane's stream, read from every lane's)
-            self._plans = {}
-        from ._lib import concurrency, current_lane
-        # (the tuning table the plan is built from is part of its identity, as in UNetModel.plan)
-        key = (B, h, w, float(scale_factor), concurrency() > 1, current_lane())
-        if key not in self._plans:
-            mine = [k for k in self._plans if k[-1] == key[-1]]
-            if len(mine) >= 4:  # (per lane: another lane's plans may be executing)
-                self._plans.pop(mine[0])
-            with torch.cuda.device(p.device), host_io():
-                self._plans[key] = VAEDecodePlan(ctx, self._packed[1], B, h, w, scale_factor)
-                self._plans[key].apply_tuning(tune_missing=os.environ.get("UPGPT_AUTOTUNE", "0") == "1")
-        return self._plans[key]
+            raise RuntimeError("upgpt_amd.AutoencoderKL.%s runs only on the MI355X HIP path (parameters are on "
+                               "%s); there is no CPU fallback" % (half, p.device))
+        with PLAN_LOCK:
+            ctx = get_context(p.device)
+            fp = weights_fingerprint(self)
+            packed = getattr(self, packed_at)
+            if packed is None or packed[0] != fp:
+                params = dict(self.named_parameters())
+                with torch.cuda.device(p.device), host_io():
+                    packed = (fp, Packed(ctx, self.arch, lambda n: params[n].data))
+                    torch.cuda.current_stream(p.device).synchronize()  # (packed on this lane's stream, read from every lane's)
+                setattr(self, packed_at, packed)
+                plans.drop(device=p.device)
+
+            def build():
+                pl = Plan(ctx, packed[1], *head)
+                pl.apply_tuning(tune_missing=autotune_missing())
+                return pl
+            return plans.get(head, build, p.device)
+
+    def _decode_plan(self, B, h, w, scale_factor):
+        from .engine import PackedVAEDecoder, VAEDecodePlan
+        return self._half_plan("decode", "_packed", self._plans, PackedVAEDecoder, VAEDecodePlan,
+                               (B, h, w, float(scale_factor)))
 
     @torch.no_grad()
     def decode(self, z, scale_factor=1.0):
@@ -121,35 +119,8 @@ class AutoencoderKL(ParamTree):
             return pl.run(z).clone()
 
     def _encode_plan(self, B, H, W):
-        from ._lib import PLAN_LOCK
-        with PLAN_LOCK:
-            return self._encode_plan_locked(B, H, W)
-
-    def _encode_plan_locked(self, B, H, W):
-        from ._lib import get_context
         from .engine import PackedVAEEncoder, VAEEncodePlan
-        p = next(self.parameters())
-        if p.device.type != "cuda":
-            raise RuntimeError("upgpt_amd.AutoencoderKL.encode runs only on the MI355X HIP path (parameters are on "
-                               "%s); there is no CPU fallback" % p.device)
-        ctx = get_context(p.device)
-        fp = weights_fingerprint(self)
-        if self._packed_enc is None or self._packed_enc[0] != fp:
-            params = dict(self.named_parameters())
-            with torch.cuda.device(p.device), host_io():
-                self._packed_enc = (fp, PackedVAEEncoder(ctx, self.arch, lambda n: params[n].data))
-                torch.cuda.current_stream(p.device).synchronize()
-            self._enc_plans = {}
-        from ._lib import concurrency, current_lane
-        key = (B, H, W, concurrency() > 1, current_lane())
-        if key not in self._enc_plans:
-            mine = [k for k in self._enc_plans if k[-1] == key[-1]]
-            if len(mine) >= 4:
-                self._enc_plans.pop(mine[0])
-            with torch.cuda.device(p.device), host_io():
-                self._enc_plans[key] = VAEEncodePlan(ctx, self._packed_enc[1], B, H, W)
-                self._enc_plans[key].apply_tuning(tune_missing=os.environ.get("UPGPT_AUTOTUNE", "0") == "1")
-        return self._enc_plans[key]
+        return self._half_plan("encode", "_packed_enc", self._enc_plans, PackedVAEEncoder, VAEEncodePlan, (B, H, W))
 
     @torch.no_grad()
     def encode(self, x):
