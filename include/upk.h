@@ -280,7 +280,9 @@ int upk_geglu_mlp_supported(upk_ctx* ctx, const upk_mlp_desc* d);
  * w_out1 / w_out2: packed [c rows][K = heads * d] (upk_pack_weight with the head padding as column map); w_q: packed
  * [heads * d rows][K = c] with the LayerNorm affine folded in (as ln_colsum weights); vec = [b_out1 (c) | colsum_q
  * (heads * d) | bias_q (heads * d) | b_out2 (c)] fp32, zero padded to a multiple of 256 floats; k_ctx [batch * n_kv, ldk],
- * vt_ctx [batch, heads, d, vt_ld] as upk_attention_f16 takes them (n_kv <= 96 <= vt_ld).  hw = rows per sample (a
+ * vt_ctx [batch, heads, d, vt_ld] as upk_attention_f16 takes them (n_kv <= 96 <= vt_ld).  Rows >= n_kv of a sample's
+ * k_ctx are never read.  Columns [n_kv, 96) of vt_ctx ARE read, and multiplied by softmax weights that are exactly 0:
+ * they must hold finite values (the engine zero-fills them; an inf or a NaN there reaches y).  hw = rows per sample (a
  * multiple of rows_per_wg: 16 or 32, 0 = 32; (c, d) = (224, 32) also 64 and 128 — m / 128 workgroups that stream the
  * weights a quarter as often, for launches that share the chip with other batches; the tile must fit 160 KB of LDS).
  * Shapes: heads = 8, (c, d) in {(224, 32), (448, 64)}. */

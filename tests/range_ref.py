@@ -40,7 +40,9 @@ e32 = 2^-24 (half an ulp of fp32, the rounding of one fp32 operation), E32 = 2^-
   accumulations acc = x W'^T and u = sum_k W'_k (W' = fp16(W gamma)).
 
 The generators (``activations``) and the case tables are shared by the host and the GPU tests; ``attn_variant_rows`` is the
-table of every compiled attention instantiation and ``attn_layout`` the two operand layouts they are run in.
+table of every compiled attention instantiation and ``attn_layout`` the two operand layouts they are run in; ``ROW_CHAIN``
+is the table of every compiled row-chain instantiation and ``cross_probe`` / ``head_probe`` / ``mlp_probe`` the operands
+that leave one stage of a chain inexact.
 """
 import math
 
@@ -490,11 +492,13 @@ def _fold(w, gamma, beta):
     return wf.to(F64), wf.float().sum(1), w @ beta
 
 
-def head_case(s, B=2, hw=64):
-    """proj_in -> t0 (fp16) -> norm1 -> q | k | v; x scaled by s."""
-    c, inner = 224, HEADS * DH
-    return dict(B=B, hw=hw, c=c, x=activations((B * hw, c), 11, s), wi=weights((c, c), c, 12), bi=vector(c, 13) * s,
-                gamma=1 + vector(c, 14, 0.2), beta=vector(c, 15), wqkv=weights((3 * inner, c), c, 16), eps=1e-5)
+def head_case(s, B=2, hw=64, c=224, dh=DH, dp=DP):
+    """proj_in -> t0 (fp16) -> norm1 -> q | k | v; x scaled by s.  c channels, HEADS heads of dh columns (dp: the padded
+    head width the kernel stores them at)."""
+    inner = HEADS * dh
+    return dict(B=B, hw=hw, c=c, heads=HEADS, dh=dh, dp=dp, x=activations((B * hw, c), 11, s), wi=weights((c, c), c, 12),
+                bi=vector(c, 13) * s, gamma=1 + vector(c, 14, 0.2), beta=vector(c, 15), wqkv=weights((3 * inner, c), c, 16),
+                eps=1e-5)
 
 
 def head_case_ref(o):
@@ -506,37 +510,47 @@ def head_case_ref(o):
     return (t0, dt0), (qkv, dqkv)
 
 
-def cross_case(s, B=2, hw=64, nkv=87):
+def cross_case(s, B=2, hw=64, nkv=87, c=224, dh=DH, dp=DP):
     """attn1.to_out (+ t0) -> t1 (fp16) -> norm2 -> to_q -> q (fp16) -> attention over the context -> a2 (fp16) ->
-    to_out (+ t1); t0 scaled by s, a1 and the context at O(1)."""
-    c, inner, M = 224, HEADS * DH, B * hw
-    return dict(B=B, hw=hw, c=c, nkv=nkv, a1=activations((M, inner), 21), t0=activations((M, c), 22, s),
+    to_out (+ t1); t0 scaled by s, a1 and the context at O(1).  c channels, HEADS heads of dh columns (dp: the padded
+    head width)."""
+    inner, M = HEADS * dh, B * hw
+    return dict(B=B, hw=hw, c=c, nkv=nkv, heads=HEADS, dh=dh, dp=dp, a1=activations((M, inner), 21),
+                t0=activations((M, c), 22, s),
                 wo1=weights((c, inner), inner, 23), bo1=vector(c, 24), gamma=1 + vector(c, 25, 0.2), beta=vector(c, 26),
                 wq=weights((inner, c), c, 27), wo2=weights((c, inner), inner, 28), bo2=vector(c, 29),
-                k=activations((B, nkv, inner), 30), v=activations((B, nkv, inner), 31), eps=1e-5, scale=DH ** -0.5)
+                k=activations((B, nkv, inner), 30), v=activations((B, nkv, inner), 31), eps=1e-5, scale=dh ** -0.5)
 
 
-def cross_case_ref(o):
+def _cross_stages(o):
+    """(t1, dt1), (q, dq), (a2, da2) of cross_case's operands, the last two [B * hw, inner]; each bound carries the ones
+    in front of it."""
     d = lambda t: t.to(F64)
-    B, hw, nkv = o["B"], o["hw"], o["nkv"]
+    B, hw, nkv, heads, dh = o["B"], o["hw"], o["nkv"], o["heads"], o["dh"]
     t1, dt1 = linear_ref(d(o["a1"]), q16(d(o["wo1"])), bias=d(o["bo1"]), res=d(o["t0"]))
     t1r = q16(t1)
     wf, u, b = _fold(o["wq"], o["gamma"], o["beta"])
     q, dq = linear_ref(t1r, wf, bias=d(b), ln=(o["eps"], d(u)), dA=dt1)
-    sp = lambda t, n: t.reshape(B, n, HEADS, DH).transpose(1, 2)
+    sp = lambda t, n: t.reshape(B, n, heads, dh).transpose(1, 2)
     a2, da2 = attention_ref(sp(q16(q), hw), sp(d(o["k"]), nkv), sp(d(o["v"]), nkv), o["scale"], dq=sp(dq, hw))
-    back = lambda t: t.transpose(1, 2).reshape(B * hw, HEADS * DH)
-    return linear_ref(q16(back(a2)), q16(d(o["wo2"])), bias=d(o["bo2"]), res=t1r, dA=back(da2), dres=dt1)
+    back = lambda t: t.transpose(1, 2).reshape(B * hw, heads * dh)
+    return (t1, dt1), (q, dq), (back(a2), back(da2))
+
+
+def cross_case_ref(o):
+    d = lambda t: t.to(F64)
+    (t1, dt1), _, (a2, da2) = _cross_stages(o)
+    return linear_ref(q16(a2), q16(d(o["wo2"])), bias=d(o["bo2"]), res=q16(t1), dA=da2, dres=dt1)
 
 
 MLP_CASES = {"mlp96": (96, 32, 0), "mlp128": (128, 64, 64)}  # M, rows per workgroup, hw (0: no GroupNorm partials)
 
 
-def mlp_case(name, s, B=None, hw=None, rows=None):
+def mlp_case(name, s, B=None, hw=None, rows=None, c=224, M=None):
     """norm3 -> GEGLU -> h (fp16) -> ff.net.2 and proj_out in one GEMM over [h | x] (+ res); x and res scaled by s.
-    B, hw, rows: a shape of the caller's (B samples of hw rows, `rows` per workgroup) instead of MLP_CASES[name]."""
-    M, rows, hw = MLP_CASES[name] if B is None else (B * hw, rows, hw)
-    c = 224
+    B, hw, rows: a shape of the caller's (B samples of hw rows, `rows` per workgroup) instead of MLP_CASES[name]; M (with
+    rows): M rows and no GroupNorm partials (hw = 0), e.g. a tail tile with rows past M."""
+    M, rows, hw = (M, rows, 0) if M is not None else MLP_CASES[name] if B is None else (B * hw, rows, hw)
     inner = 4 * c
     return dict(M=M, rows=rows, hw=hw, c=c, inner=inner, x=norm_input((M, c), 41 + M, s), res=activations((M, c), 42, s),
                 gamma=1 + vector(c, 43, 0.2), beta=vector(c, 44), w1=weights((2 * inner, c), c, 45), b1=vector(2 * inner, 46),
@@ -550,6 +564,197 @@ def mlp_case_ref(o):
     A = torch.cat([q16(h), d(o["x"])], -1)
     W = torch.cat([q16(d(o["w2h"])), q16(d(o["w2x"]))], -1)
     return linear_ref(A, W, bias=d(o["b2"]), res=d(o["res"]), dA=torch.cat([dh, torch.zeros_like(d(o["x"]))], -1))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# every compiled row-chain instantiation, and operands that make all stages but one exact, so that the output is held to
+# that stage's own bound.  Shared by tests/test_row_chain_stages_{host,gpu}.py.
+MLP_STREAM = 0x1000  # include/upk.h UPK_MLP_STREAM
+XBLOCK_FAMILIES = {(224, 32): 28, (448, 64): 56}  # (c, padded head dim) -> real head dim; inner = 8 dh = c in both
+ROW_CHAIN_DEFAULT_ROWS = {"xblock": 32, "hblock": 32, "mlp": 64}  # what rows_per_wg = 0 means
+STAGE_SCALES = (1, 2 ** 10)   # the scale of the residual stream in the single-stage probes (the full chains: SCALES)
+X2_NKV = (1, 16, 17, 80, 87, 96)  # both sides of a 16-key fragment edge, the production 87, the unmasked 96
+X2_KEY_SCALES = (1, 4)        # diffuse and peaked softmax (ATTN_VARIANT_SCALES' logit gains)
+GN_FOLD = dict(groups=32, eps=1e-6, ld_extra=32)
+
+
+def _row_chain():
+    rows = []
+    for (c, d), dh in XBLOCK_FAMILIES.items():
+        for r in ((16, 32, 64, 128) if c == 224 else (16, 32)):
+            rows.append(dict(kind="xblock", c=c, d=d, dh=dh, rows=r, stream=False, gn=False))
+    for r in (16, 32, 64, 128):
+        for gn in (False, True):
+            rows.append(dict(kind="hblock", c=224, d=32, dh=28, rows=r, stream=False, gn=gn))
+    for r, st in ((32, False), (64, False), (128, True), (64, True)):
+        rows.append(dict(kind="mlp", c=224, d=0, dh=0, rows=r, stream=st, gn=False))
+    return rows
+
+
+ROW_CHAIN = _row_chain()
+
+
+def row_chain_key(row):
+    return (row["kind"], row["c"], row["d"], row["rows"], row["stream"], row["gn"])
+
+
+def row_chain_id(row):
+    return "%s-c%d-rows%d%s%s" % (row["kind"], row["c"], row["rows"], "s" if row["stream"] and row["rows"] != 128 else "",
+                                  "-gn" if row["gn"] else "")
+
+
+def row_chain_shapes(row):
+    """(B, hw, M) of a table row: one workgroup per sample (the sample boundary, the per-sample K / V^T bases), two tiles
+    per sample (tok0 of the V^T store, the partial-block index), and for the MLP a tail tile with rows past M (hw = 0)."""
+    r = row["rows"]
+    shapes = [(2, r, 2 * r), (2, 2 * r, 4 * r)]
+    if row["kind"] == "mlp":
+        shapes.append((1, 0, r + 8))
+    return shapes
+
+
+def mlp_rows_per_wg(row):
+    """The descriptor's rows_per_wg of an MLP table row."""
+    return row["rows"] | (MLP_STREAM if row["stream"] and row["rows"] != 128 else 0)
+
+
+def cross_probe(probe, s, B, hw, nkv, c=224, dh=DH, dp=DP, ks=1):
+    """cross_case's operands with all stages but one made exact (ks multiplies the context keys):
+      'X1'  w_q = 0, so q = 0 and every softmax is uniform over finite values; w_out2 = 0, b_out2 = 0, so the last GEMM
+            adds exact zeros to the t1 the kernel keeps as fp16: y = fp16(t1), the first GEMM alone.
+      'X2'  a1 = 0, b_out1 = 0: t1 = fp16(0 + 0 + t0) = t0 exactly.  w_out2 = I (inner = c), b_out2 = 0: every dot product
+            of the last GEMM is one fp16 value times 1 plus exact zeros, so y = fp16(fp16(a2) + t0): LayerNorm, the query
+            projection and the attention, then one fp32 addition and the output rounding.
+      'X3'  as X2 with the general w_out2 / b_out2: the last GEMM behind the seam of a2.
+      'X4'  the full chain."""
+    o = cross_case(s, B=B, hw=hw, nkv=nkv, c=c, dh=dh, dp=dp)
+    o["probe"], o["ks"] = probe, ks
+    if ks != 1:
+        o["k"] = (o["k"] * float(ks)).half()
+    if probe == "X1":
+        o["wq"], o["wo2"], o["bo2"] = torch.zeros_like(o["wq"]), torch.zeros_like(o["wo2"]), torch.zeros_like(o["bo2"])
+    elif probe in ("X2", "X3"):
+        o["a1"], o["bo1"] = torch.zeros_like(o["a1"]), torch.zeros_like(o["bo1"])
+        if probe == "X2":
+            assert HEADS * dh == c
+            o["wo2"], o["bo2"] = torch.eye(c), torch.zeros_like(o["bo2"])
+    else:
+        assert probe == "X4"
+    return o
+
+
+def _attention_behind_ln(o, t):
+    """(a2, da2) [B * hw, inner] of cross_case's attention over rows t that are exact (no seam in front)."""
+    d = lambda v: v.to(F64)
+    B, hw, nkv, heads, dh = o["B"], o["hw"], o["nkv"], o["heads"], o["dh"]
+    wf, u, b = _fold(o["wq"], o["gamma"], o["beta"])
+    q, dq = linear_ref(t, wf, bias=d(b), ln=(o["eps"], d(u)))
+    sp = lambda v, n: v.reshape(B, n, heads, dh).transpose(1, 2)
+    a2, da2 = attention_ref(sp(q16(q), hw), sp(d(o["k"]), nkv), sp(d(o["v"]), nkv), o["scale"], dq=sp(dq, hw))
+    back = lambda v: v.transpose(1, 2).reshape(B * hw, heads * dh)
+    return back(a2), back(da2)
+
+
+def cross_probe_ref(o):
+    """(ref, bound) of y for cross_probe's operands: the inexact stage's own bound, no term for the exact ones."""
+    d = lambda t: t.to(F64)
+    probe, t0 = o["probe"], d(o["t0"])
+    if probe == "X1":
+        return linear_ref(d(o["a1"]), q16(d(o["wo1"])), bias=d(o["bo1"]), res=t0)
+    if probe == "X4":
+        return cross_case_ref(o)
+    a2, da2 = _attention_behind_ln(o, t0)
+    if probe == "X3":
+        return linear_ref(q16(a2), q16(d(o["wo2"])), bias=d(o["bo2"]), res=t0, dA=da2)
+    y = a2 + t0  # X2: da2 holds the rounding of a2 to fp16; then one fp32 addition and the output rounding
+    return y, da2 + E32H * (a2.abs() + t0.abs()) + u16(y)
+
+
+def head_probe(probe, s, B, hw, c=224, dh=DH, dp=DP):
+    """head_case's operands:
+      'H1'  the full chain; t0 is a direct output and is checked at linear_ref's bound, q | k | v behind its seam.
+      'H2'  w_in = I, b_in = 0: every dot product of the first GEMM is one fp16 value times 1 plus exact zeros, so
+            t0 = x bit for bit and q | k | v are the folded-LayerNorm GEMM alone.
+      'F1', 'F2'  the GroupNorm fold: x is the un-normalised input, whose per-(row block, channel) partial sums the test
+            supplies (fp32 sums of hw / nblk rows each, nblk = max(1, hw / 16), leading dimension c + 32).  F2 has w_in = I,
+            b_in = 0, so t0 = fp16(GroupNorm(x)) and q | k | v lie one seam behind it; F1 is the full chain behind it."""
+    o = head_case(s, B=B, hw=hw, c=c, dh=dh, dp=dp)
+    o["probe"] = probe
+    if probe in ("H2", "F2"):
+        o["wi"], o["bi"] = torch.eye(c), torch.zeros_like(o["bi"])
+    if probe in ("F1", "F2"):
+        o["x"] = norm_input((B * hw, c), 17, s)
+        nblk = max(1, hw // 16)
+        xf = o["x"].float().reshape(B, nblk, hw // nblk, c)
+        part = torch.zeros(B, nblk, 2, c + GN_FOLD["ld_extra"])
+        part[..., :c] = torch.stack([xf.sum(2), (xf * xf).sum(2)], 2)
+        o.update(gn_part=part, gn_nblk=nblk, gn_gamma=1 + vector(c, 18, 0.3), gn_beta=vector(c, 19, 0.2),
+                 gn_groups=GN_FOLD["groups"], gn_eps=GN_FOLD["eps"])
+    else:
+        assert probe in ("H1", "H2")
+    return o
+
+
+def head_probe_ref(o):
+    """((t0, dt0), (qkv, dqkv)); H2: dt0 is None, t0 must equal x bit for bit.  The GroupNorm statistics of the fold come
+    from exact fp32 partials of hw / nblk terms each, summed over nblk blocks in fp32 and over the group's channels in
+    fp64: at most hw / nblk + nblk terms per channel, inside the hw c / groups terms groupnorm_ref allows for."""
+    d = lambda t: t.to(F64)
+    probe = o["probe"]
+    if probe == "H1":
+        return head_case_ref(o)
+    wf, u, b = _fold(o["wqkv"], o["gamma"], o["beta"])
+    ln = (o["eps"], d(u))
+    if probe == "H2":
+        return (d(o["x"]), None), linear_ref(d(o["x"]), wf, bias=d(b), ln=ln)
+    B, hw, c = o["B"], o["hw"], o["c"]
+    gn, dgn = groupnorm_ref(d(o["x"]).reshape(B, hw, c), o["gn_groups"], d(o["gn_gamma"]), d(o["gn_beta"]), o["gn_eps"], False)
+    gn, dgn = gn.reshape(B * hw, c), dgn.reshape(B * hw, c)
+    if probe == "F2":
+        return (gn, dgn), linear_ref(q16(gn), wf, bias=d(b), ln=ln, dA=dgn)
+    t0, dt0 = linear_ref(q16(gn), q16(d(o["wi"])), bias=d(o["bi"]), dA=dgn)
+    return (t0, dt0), linear_ref(q16(t0), wf, bias=d(b), ln=ln, dA=dt0)
+
+
+def mlp_probe(probe, s, B, hw, rows, c=224, M=None):
+    """mlp_case's operands:
+      'M1'  w2h = 0: the hidden tile is finite and meets exact zeros, y = res + x W2x^T + b2, the second GEMM alone.
+      'M2j' (j = 0..3)  w2x = 0, b2 = 0, res = 0 and w2h selects the hidden columns [c j, c j + c): every dot product is
+            one fp16 value times 1 plus exact zeros, so y = fp16(h) on those columns: LayerNorm and GEGLU alone.  The four
+            probes cover every hidden column, hence both LDS slices of the streaming form at every position.
+      'M3'  the full chain (and the GroupNorm partials it leaves)."""
+    o = mlp_case("probe", s, B=B, hw=hw, rows=rows, c=c) if M is None else mlp_case("probe", s, rows=rows, c=c, M=M)
+    o["probe"] = probe
+    if probe == "M1":
+        o["w2h"] = torch.zeros_like(o["w2h"])
+    elif probe.startswith("M2"):
+        j = int(probe[2:])
+        sel = torch.zeros_like(o["w2h"])
+        sel[torch.arange(c), c * j + torch.arange(c)] = 1.0
+        o.update(w2h=sel, w2x=torch.zeros_like(o["w2x"]), b2=torch.zeros_like(o["b2"]), res=torch.zeros_like(o["res"]))
+    else:
+        assert probe == "M3"
+    return o
+
+
+def mlp_hidden_ref(o):
+    """(h, dh) [M, inner]: the GEGLU hidden tile of mlp_case's operands at its single-stage bound."""
+    d = lambda t: t.to(F64)
+    wf, u, b = _fold(o["w1"], o["gamma"], o["beta"])
+    return linear_ref(d(o["x"]), wf, bias=d(o["b1"] + b), act="geglu", ln=(o["eps"], d(u)))
+
+
+def mlp_probe_ref(o, hidden=None):
+    """(ref, bound) of y; hidden: mlp_hidden_ref(o) computed before (the four M2 probes share it)."""
+    d = lambda t: t.to(F64)
+    probe, c = o["probe"], o["c"]
+    if probe == "M1":
+        return linear_ref(d(o["x"]), q16(d(o["w2x"])), bias=d(o["b2"]), res=d(o["res"]))
+    if probe == "M3":
+        return mlp_case_ref(o)
+    j = int(probe[2:])
+    h, dh = hidden if hidden is not None else mlp_hidden_ref(o)
+    return h[:, c * j:c * j + c], dh[:, c * j:c * j + c]
 
 
 QPROJ = dict(C=224, heads=8, dh=28, nq=64, nkv=87)

@@ -238,18 +238,20 @@ def _emulate_attention(o, **kw):
     return _attn32(sp(o["q"], o["nq"]), sp(o["k"], o["nkv"]), sp(o["v"], o["nkv"]), o["scale"], o["causal"], **kw)
 
 
-def _lnlin32(x, w, gamma, beta, eps, extra_bias=None):
-    """The folded-LayerNorm Linear in fp32: one-pass statistics, (acc - mean u) rstd + b."""
+def _lnlin32(x, w, gamma, beta, eps, extra_bias=None, stat_cols=None):
+    """The folded-LayerNorm Linear in fp32: one-pass statistics, (acc - mean u) rstd + b.  (stat_cols, a defect: the
+    statistics are taken over the first stat_cols columns only.)"""
     wf = (w * gamma[None, :]).half().float()
     b = w @ beta if extra_bias is None else w @ beta + extra_bias
-    mean = x.mean(-1, keepdim=True)
-    rstd = torch.rsqrt(((x * x).mean(-1, keepdim=True) - mean * mean).clamp(min=0) + eps)
+    xs = x if stat_cols is None else x[:, :stat_cols]
+    mean = xs.mean(-1, keepdim=True)
+    rstd = torch.rsqrt(((xs * xs).mean(-1, keepdim=True) - mean * mean).clamp(min=0) + eps)
     return (x @ wf.t() - mean * wf.sum(1)) * rstd + b
 
 
-def emulate_head(o):
+def emulate_head(o, stat_cols=None):
     t0 = (o["x"].float() @ o["wi"].half().float().t() + o["bi"]).half()
-    return t0, _lnlin32(t0.float(), o["wqkv"], o["gamma"], o["beta"], o["eps"]).half()
+    return t0, _lnlin32(t0.float(), o["wqkv"], o["gamma"], o["beta"], o["eps"], stat_cols=stat_cols).half()
 
 
 def emulate_cross(o, stale_t1=False):
@@ -257,17 +259,19 @@ def emulate_cross(o, stale_t1=False):
     t1 = o["a1"].float() @ o["wo1"].half().float().t() + o["bo1"] + o["t0"].float()
     t1 = t1.half().float()
     q = _lnlin32(t1, o["wq"], o["gamma"], o["beta"], o["eps"]).half().float()
-    sp = lambda t, n: t.float().reshape(B, n, R.HEADS, R.DH).transpose(1, 2)
+    sp = lambda t, n: t.float().reshape(B, n, o["heads"], o["dh"]).transpose(1, 2)
     a2 = _attn32(sp(q, hw), sp(o["k"], nkv), sp(o["v"], nkv), o["scale"]).float().transpose(1, 2).reshape(B * hw, -1)
     # (stale_t1, a defect: the final residual reads t0 where it should read t1)
     return (a2 @ o["wo2"].half().float().t() + o["bo2"] + (o["t0"].float() if stale_t1 else t1)).half()
 
 
-def emulate_mlp(o, drop_last_chunk=False):
+def emulate_mlp(o, drop_last_chunk=False, gelu=F.gelu, stale_slice=False):
     inner = o["inner"]
     pre = _lnlin32(o["x"].float(), o["w1"], o["gamma"], o["beta"], o["eps"], extra_bias=o["b1"])
-    h = pre[:, :inner] * F.gelu(pre[:, inner:])
+    h = pre[:, :inner] * gelu(pre[:, inner:])
     h = h.half().float()
+    if stale_slice:  # (a defect: hidden columns 128..255 are a stale copy of 0..127, the streaming form's slice hazard)
+        h[:, 128:256] = h[:, :128]
     kx = o["c"] - 32 if drop_last_chunk else o["c"]  # (a defect: the last 32-wide K chunk of the GEMM over [h | x] dropped)
     return (h @ o["w2h"].half().float().t() + o["x"].float()[:, :kx] @ o["w2x"].half().float()[:, :kx].t() + o["b2"]
             + o["res"].float()).half()
