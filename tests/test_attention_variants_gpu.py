@@ -2,8 +2,9 @@
 waves per workgroup, against range_ref.attention_ref's fp64 reference and derived bound, at the shapes of
 range_ref.attn_variant_rows() (the smallest that reach each code path), at three softmax regimes and in two operand
 layouts: dense, and the production one (q | k as column halves of one buffer, a wider vt_ld whose unused columns hold NaN,
-out inside a sentinel-filled buffer).  Then the census: every attention launch of the plans the benchmark replays, with
-the variant it takes at the production batch, and a replica of it at batch 2 under that variant.
+out inside a sentinel-filled buffer).  Then the census: every attention launch of the plans the benchmark replays and of
+the guided UNet, upscale UNet, VAE encoder and image tower plans, with the variant it takes at the production batch, and a
+replica of it at batch 2 under that variant.
 
 tests/test_attention_variants_host.py shows that the criterion passes a faithful tiled emulation and fails on seeded
 defects.  The fp64 references are computed on the device that holds the operands."""
@@ -14,7 +15,8 @@ import torch
 
 import range_ref as R
 from test_production_launches_gpu import B as PROD_B
-from test_production_launches_gpu import model, unet_plan  # noqa: F401  (model: the fixture)
+import test_production_launches_gpu as P
+from test_production_launches_gpu import model, towers, unet_plan, upscale_models  # noqa: F401  (the fixtures)
 from upgpt_amd import _lib as L
 
 pytestmark = pytest.mark.gpu
@@ -359,3 +361,35 @@ def test_census_of_the_unet_plans(ctx, model, H, W, lanes):
 @pytest.mark.parametrize("h,w", [(32, 32), (32, 24)])
 def test_census_of_the_vae_decoder_plans(ctx, model, h, w):
     census(ctx, model.first_stage_model._decode_plan(PROD_B, h, w, 0.18215), "VAE decoder %dx%d B = %d" % (h, w, PROD_B))
+
+
+# ------------------------------------------------------------------- the plans beyond the headline (built as P names them)
+@pytest.mark.parametrize("lanes", [1, 4], ids=["single", "shared_chip4"])
+@pytest.mark.parametrize("H,W", [(32, 32), (32, 24)])
+def test_census_of_the_guided_unet_plans(ctx, model, H, W, lanes):
+    plan = P.in_lanes(lanes, lambda: model.model.diffusion_model.plan(2 * PROD_B, H, W, P.NCTX, P.STEPS, "sampler"))
+    census(ctx, plan, "guided UNet %dx%d 2B = %d, %s" % (H, W, 2 * PROD_B, P.lanes_title(lanes)))
+
+
+@pytest.mark.parametrize("lanes", [1, 4], ids=["single", "shared_chip4"])
+@pytest.mark.parametrize("h,w", P.UP_LATENTS)
+def test_census_of_the_upscale_unet_plans(ctx, upscale_models, h, w, lanes):
+    unet = upscale_models((h, w)).model.diffusion_model
+    plan = P.in_lanes(lanes, lambda: unet.plan(P.UP_B, h, w, P.UP_NCTX, P.STEPS, "sampler"))
+    census(ctx, plan, "upscale UNet %dx%d B = %d, %s" % (h, w, P.UP_B, P.lanes_title(lanes)))
+
+
+@pytest.mark.parametrize("H,W", [(256, 256), (256, 192)])
+def test_census_of_the_vae_encoder_plans(ctx, model, H, W):
+    census(ctx, model.first_stage_model._encode_plan(PROD_B, H, W), "VAE encoder %dx%d B = %d" % (H, W, PROD_B))
+
+
+def test_census_of_the_image_tower_plan(ctx, towers):
+    """ViT-L/14 at N = 8 x 9 crops: 24 launches of one shape, 16 heads of 64 over 257 tokens (vt_ld 288).  The laion
+    stage's image tower has the same dimensions and so the same launch.  Not here: the text tower's causal kernel and the
+    cross stage's few-keys kernel are single-variant; tests/test_clip_gpu.py and tests/test_laion_cond_gpu.py run them at
+    their production head and token counts."""
+    title, build = P.tower_plan(towers, "image")
+    plan = build()
+    assert len(plan_attention(plan)) == plan.cfg["layers"] == 24
+    census(ctx, plan, title)

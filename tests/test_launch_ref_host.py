@@ -152,6 +152,96 @@ def test_folded_layernorm_against_layer_norm_then_linear(rows_in, geglu):
     assert float((ref - want).abs().max()) <= 1e-5 and float(((ref - want).abs() / bound).max()) < 0.05
 
 
+def test_folded_layernorm_with_quickgelu_against_layer_norm_linear_and_the_sigmoid_form():
+    """The fc1 launch of the CLIP towers: LayerNorm folded into the GEMM, UPK_F_QUICKGELU in its epilogue."""
+    M, c1, N = 21, 96, 160
+    o = operands(1, M, 1, c1, N, seed=40)
+    o["x1"] = R.norm_input((1, M, 1, c1), 41, 1)
+    o["ln_colsum"] = w16(o["w"])[:, :, 0, 0].sum(1).float()
+    f = LR.fields(batch=1, in_h=M, in_w=1, c1=c1, ld1=c1, x1=True, ksize=1, stride=1, n_out=N, n_pad=N, bias=True,
+                  ln_colsum=True, ln_eps=1e-5, ln_dim=c1, flags=L.F_QUICKGELU, ldy=N)
+    assert LR.unhandled(f) == []
+    ref, bound = LR.launch_ref(f, o)["y"]
+    h = F.linear(F.layer_norm(d64(o["x1"][0, :, 0]), (c1,), None, None, 1e-5), w16(o["w"])[:, :, 0, 0], d64(o["bias"]))
+    want = h * torch.sigmoid(1.702 * h)
+    # (u is the fp32 sum the kernel is given, PyTorch's the exact one: as in the test above)
+    assert float((ref - want).abs().max()) <= 1e-5 and float(((ref - want).abs() / bound).max()) < 0.05
+    plain, _ = LR.launch_ref(dict(f, flags=0), o)["y"]
+    assert float((plain - ref).abs().max()) > 0.1  # (the activation is not a no-op on these operands)
+
+
+@pytest.fixture(scope="module")
+def odd_tokens_vt():
+    """The towers' q | k | v launch in small: folded LayerNorm, V^T tail, 3 samples of 7 tokens (M = 21 rows: no power of
+    two divides the sample boundaries, so an M tile of any height straddles them), 2 heads of 8, vt_ld = 32."""
+    B, tok, c1, heads, dh = 3, 7, 64, 2, 8
+    hd = heads * dh
+    o = operands(B, tok, 1, c1, 3 * hd, seed=50)
+    o["x1"] = R.norm_input((B, tok, 1, c1), 51, 1)
+    o["ln_colsum"] = w16(o["w"])[:, :, 0, 0].sum(1).float()
+    f = LR.fields(batch=B, in_h=tok, in_w=1, c1=c1, ld1=c1, x1=True, ksize=1, stride=1, n_out=2 * hd, n_pad=3 * hd, bias=True,
+                  ldy=2 * hd, ln_colsum=True, ln_eps=1e-5, ln_dim=c1, vt=True, vt_from=2 * hd, vt_heads=heads, vt_dhead=dh,
+                  vt_ld=32, vt_tokens=tok)
+    assert LR.unhandled(f) == []
+    return f, o, LR.launch_ref(f, o)
+
+
+def test_folded_layernorm_with_a_transposed_tail_at_an_odd_token_count_against_a_permute(odd_tokens_vt):
+    f, o, out = odd_tokens_vt
+    B, tok, c1, heads, dh = f["batch"], f["vt_tokens"], f["c1"], f["vt_heads"], f["vt_dhead"]
+    hd = heads * dh
+    x = d64(o["x1"]).reshape(B * tok, c1)
+    full = F.linear(F.layer_norm(x, (c1,), None, None, 1e-5), w16(o["w"])[:, :, 0, 0], d64(o["bias"]))
+    assert out["y"][0].shape == (B * tok, 2 * hd) and out["vt"][0].shape == out["vt"][1].shape == (B, heads, dh, tok)
+    assert float((out["y"][0] - full[:, :2 * hd]).abs().max()) <= 1e-5
+    want = torch.empty(B, heads, dh, tok, dtype=F64)
+    for b in range(B):  # (an independent permute: element by element from the row of (sample, token))
+        for t in range(tok):
+            want[b, :, :, t] = full[b * tok + t, 2 * hd:].reshape(heads, dh)
+    assert float((out["vt"][0] - want).abs().max()) <= 1e-5
+    assert float(((out["vt"][0] - want).abs() / out["vt"][1]).max()) < 0.05
+    assert R.ratio(R.q16(out["vt"][0]), *out["vt"]) <= 1
+
+
+def test_a_tile_that_ignores_the_sample_boundary_fails_at_an_odd_token_count(odd_tokens_vt):
+    """Row 7 of the GEMM is (sample 1, token 0).  A tile that computes the V^T address as if the rows of its tile all
+    belonged to the tile's first sample puts that row's values where sample 0's token 7 would be — for one element that
+    is the slot of sample 0's LAST token, column 6 shifted by one: the value lands in [0, h, e, 6]."""
+    f, _, out = odd_tokens_vt
+    ref, bound = out["vt"]
+    tok = f["vt_tokens"]
+    for h, e in ((0, 0), (1, 5)):
+        got = R.q16(ref)
+        got[0, h, e, tok - 1] = got[1, h, e, 0]
+        assert got[0, h, e, tok - 1] != R.q16(ref)[0, h, e, tok - 1]
+        assert R.ratio(got, ref, bound) > 1
+    for at in ((0, 0, 0, tok - 1), (1, 0, 0, 0), (2, 1, 7, 3)):
+        for sign in (1, -1):
+            got = R.q16(ref)
+            got[at] += sign * 4 * R.u16(got[at])
+            assert R.ratio(got, ref, bound) > 1
+
+
+def test_plain_gemm_of_8_rows_with_fp32_output_against_linear():
+    """The pooled projection of the text tower: M = batch rows, no bias, fp32 rows."""
+    M, c1, N = 8, 96, 64
+    o = operands(M, 1, 1, c1, N, seed=60)
+    f = LR.fields(batch=M, in_h=1, in_w=1, c1=c1, ld1=c1 + 32, x1=True, ksize=1, stride=1, n_out=N, n_pad=N,
+                  flags=L.F_OUT_F32, ldy=N)
+    assert LR.unhandled(f) == []
+    ref, bound = LR.launch_ref(f, o)["y"]
+    want = F.linear(d64(o["x1"][:, 0, 0, :c1]), w16(o["w"])[:, :, 0, 0])
+    close(ref, want)
+    assert ref.shape == (M, N) and bool((bound >= R.E32 * want.abs()).all())
+    # fp32 rows: the bound has no fp16 output rounding in it, so a correctly rounded fp32 output passes and one that
+    # went through fp16 on the way does not
+    assert R.ratio(d64(ref.float()), ref, bound) <= 1
+    assert R.ratio(R.q16(ref), ref, bound) > 1
+    got = ref.clone()
+    got[M - 1] = want[M - 2]  # (the last row computed from its neighbour's input)
+    assert R.ratio(got, ref, bound) > 1
+
+
 def test_phase_form_equals_the_direct_3x3_on_weights_that_need_no_rounding():
     """Weights k / 64 with |k| <= 8: they and every sum of up to four taps are fp16 numbers, so neither form rounds
     anything and the four 2x2 convs on the low-resolution grid ARE the 3x3 conv on the upsampled one, exactly."""

@@ -1,13 +1,19 @@
-"""Every conv / GEMM launch of the plans the headline benchmark replays, at the shape and the (tile configuration,
-split-K) it runs with, against the fp64 reference of tests/launch_ref.py.
+"""Every conv / GEMM launch of the production plans, at the shape and the (tile configuration, split-K) it runs with,
+against the fp64 reference of tests/launch_ref.py.
 
 The plans are built, never run: bbox UNet at B = 8, 87 context tokens, latent 32x32 and 32x24, once under the single-forward
 table and once inside shared_chip(4) (lanes overlay, other lowering), and the VAE decoder at B = 8 for both latents (one
-case per resolution level: its 256x256 level alone is M = 524288 rows).  For each distinct launch of a plan a REPLICA
-descriptor carries every shape, flag, stride, leading dimension and choice of the production descriptor, while every
-pointer goes to operands this test owns: the production buffers and weights are never touched.  One launch, then
-``range_ref.ratio(got, ref, bound) <= 1`` for the output and for every by-product.  tests/test_launch_ref_host.py shows
-that this criterion fails on a subtly wrong output."""
+case per resolution level: its 256x256 level alone is M = 524288 rows): the headline benchmark's.  Then the plans behind
+its secondary figures and behind test_step / edit_region / validation_step: the guided sampler's UNet plan
+(2B = 16 rows), the upscale UNet at B = 4 (64x64 and 128x96, one case per level) and its kl-f4 decoder, the VAE encoder,
+the CLIP text tower (hidden states and pooled), the ViT-L/14 image tower at 72 crops, the laion stage's two towers and its
+cross stage, and LPIPS for one pair.  Inside shared_chip(4) those plans launch only what differs from their single-forward
+lowering.
+
+For each distinct launch of a plan a REPLICA descriptor carries every shape, flag, stride, leading dimension and choice of
+the production descriptor, while every pointer goes to operands this test owns: the production buffers and weights are
+never touched.  One launch, then ``range_ref.ratio(got, ref, bound) <= 1`` for the output and for every by-product.
+tests/test_launch_ref_host.py shows that this criterion fails on a subtly wrong output."""
 import ctypes as C
 import re
 import time
@@ -285,9 +291,17 @@ def variant(d, key):
             bool(d.ln_rows_out), bool(d.ln_rows_in), bool(d.bias), bool(d.pf_next))
 
 
-def check_plan(ctx, plan, title, lanes, select=lambda d: True):
+def variants(plan):
+    return {variant(d, key) for d, key in plan.convs}
+
+
+def check_plan(ctx, plan, title, lanes, select=lambda d: True, known=None):
+    """known: variants checked elsewhere (the single-forward plan's, when `plan` is the same network lowered under
+    shared_chip): an entry that repeats one of them is covered by that check and only what differs is launched here —
+    which may be nothing."""
     t0 = time.perf_counter()
-    seen, triples, peak, fails, cache = set(), set(), {}, [], {}
+    seen, triples, peak, fails, cache = set(known or ()), set(), {}, [], {}
+    n_known = len(seen)
     tables = {"lanes table": 0, "single-forward table": 0, "cost model": 0}
     compared = {}
     n_sel = 0
@@ -310,11 +324,14 @@ def check_plan(ctx, plan, title, lanes, select=lambda d: True):
         tables[tab] = tables.get(tab, 0) + 1
     # coverage: every selected entry is a checked variant, or a repeat of one
     assert all(variant(d, key) in seen for d, key in plan.convs if select(d))
-    assert n_sel > 0 and len(seen) >= len(triples) > 0
-    print("\n%s: %d launches, %d distinct (key, tile configuration, split-K), %d checked (by-product variants apart); "
-          "pinned: %s; %.1f s" % (title, n_sel, len(triples), len(seen),
+    n_checked = len(seen) - n_known
+    assert n_sel > 0 and n_checked >= len(triples) and (len(triples) > 0 or known is not None)
+    print("\n%s: %d launches, %d distinct (key, tile configuration, split-K), %d checked (by-product variants apart)%s; "
+          "pinned: %s; %.1f s" % (title, n_sel, len(triples), n_checked,
+                                  "" if known is None else " = what differs from the single-forward plan's %d" % n_known,
                                   ", ".join("%d by the %s" % (n, t) for t, n in tables.items()), time.perf_counter() - t0))
     print("    compared: " + ", ".join("%s x %d" % kv for kv in sorted(compared.items())))
+    print("    %d of the %d launches fall to the cost model" % (sum(d.tune_cfg == 0 for d, _ in plan.convs if select(d)), n_sel))
     for cls in sorted(peak):
         print("    %-40s largest ratio %.3f" % (cls, peak[cls]))
     assert not fails, "%d check(s) failed:\n%s" % (len(fails), "\n".join(fails))
@@ -343,14 +360,247 @@ def test_vae_decoder_plan_launches_against_fp64(ctx, model, h, w, level):
     assert sum(rows(d) == by_level[level] for d, _ in plan.convs) == n
 
 
+# ------------------------------------------------------------------------------------------- the plans beyond the headline
+# Each is built through the call the product makes (the call site is named), on synthetic weights as bench.py's
+# encoders_secondary / upscale_secondary fill them, and never run.
+UP_B, UP_NCTX = 4, 86                  # bench.py upscale_secondary: bs = 4, 86 context tokens
+UP_LATENTS = [(64, 64), (128, 96)]     # the latent BASELINE words, and the one the upscale config states
+N_STYLES = 9                           # style crops per sample (bench.py encoders_secondary; the laion stage's golden)
+LPIPS_SIZES = [(256, 176)]             # crop_size of the bbox config: the pictures test_step writes and run_metrics scores
+
+
+def rows_of(d):
+    Ho, Wo = LR.out_dims(LR.fields(d))
+    return d.batch * Ho * Wo
+
+
+def in_lanes(lanes, build):
+    if lanes > 1:
+        with L.shared_chip(lanes):
+            return build()
+    return build()
+
+
+def lanes_title(lanes):
+    return "shared_chip(4)" if lanes > 1 else "single forward"
+
+
+def check_lowerings(ctx, build, title, lanes):
+    """lanes = 1: every launch of the plan.  lanes = 4: the same network lowered inside shared_chip(4); only the launches
+    whose variant() differs from the single-forward plan's are launched (none is a valid result, and is printed)."""
+    single = build() if lanes > 1 else None
+    plan = in_lanes(lanes, build)
+    assert lanes == 1 or plan is not single
+    known = None if single is None else variants(single)
+    n = check_plan(ctx, plan, "%s, %s" % (title, lanes_title(lanes)), lanes, known=known)
+    if known is not None:
+        print("    %d of the %d variants of the shared_chip(4) plan differ from the single-forward plan's" % (
+            len(variants(plan) - known), len(variants(plan))))
+    return plan, n
+
+
+def check_levels(ctx, plan, title, levels, level, lanes=1, known=None):
+    """One resolution level of a plan: `levels` maps a case name to the row counts it owns; a launch that belongs to no
+    case fails every case, so the cases of a plan cover len(plan.convs) together."""
+    owned = [m for ms in levels.values() for m in ms]
+    assert len(owned) == len(set(owned))
+    stray = sorted({rows_of(d) for d, _ in plan.convs} - set(owned))
+    assert not stray, "%s: launches of %s rows belong to no case" % (title, stray)
+    assert sum(sum(rows_of(d) in ms for d, _ in plan.convs) for ms in levels.values()) == len(plan.convs)
+    mine = levels[level]
+    n = check_plan(ctx, plan, "%s, %s (M = %s)" % (title, level, " / ".join(str(m) for m in mine)), lanes,
+                   select=lambda d: rows_of(d) in mine, known=known)
+    assert n == sum(rows_of(d) in mine for d, _ in plan.convs)
+    return n
+
+
+def drop_plans(*modules):
+    """Module end: the plans (buffers, packed weights) of the fixtures' modules go, and the allocator's cache with them."""
+    from upgpt_amd.plancache import PlanCache
+    torch.cuda.synchronize()
+    for m in modules:
+        for sub in m.modules():
+            for v in list(vars(sub).values()):
+                if isinstance(v, PlanCache):
+                    v.drop(device=DEV)
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("lanes", [1, 4], ids=["single", "shared_chip4"])
+@pytest.mark.parametrize("H,W", [(32, 32), (32, 24)])
+def test_guided_unet_plan_launches_against_fp64(ctx, model, H, W, lanes):
+    """DDIMSampler._fast_sampling with unconditional guidance: unet.plan(2 b, H, W, n_ctx, S, "sampler"), b = 8."""
+    build = lambda: model.model.diffusion_model.plan(2 * B, H, W, NCTX, STEPS, "sampler")
+    plan, n = check_lowerings(ctx, build, "guided UNet %dx%d (2B = %d rows)" % (H, W, 2 * B), lanes)
+    assert (plan.B, plan.H, plan.W, plan.n_ctx, plan.rows) == (2 * B, H, W, NCTX, STEPS)
+    assert n == len(plan.convs)
+
+
+@pytest.fixture(scope="module")
+def upscale_models():
+    """{(h, w): the upscale model as bench.py's upscale_secondary builds it}, built on first use."""
+    import upgpt_amd
+    from upgpt_amd import synth
+    made = {}
+
+    def get(hw):
+        if hw not in made:
+            m = upgpt_amd.build_model("upscale", overrides={"image_size": list(hw)})
+            synth.fill_module_(m)
+            made[hw] = m.cuda()
+        return made[hw]
+
+    yield get
+    drop_plans(*made.values())
+    made.clear()
+    torch.cuda.empty_cache()
+
+
+def upscale_unet_levels(h, w):
+    lv = {"prep": (STEPS, UP_B * UP_NCTX)}  # time embedding / emb_layers rows, and the context k | v projections
+    lv.update({"level %d" % k: (UP_B * h * w // 4 ** k,) for k in range(4)})
+    return lv
+
+
+@pytest.mark.parametrize("lanes", [1, 4], ids=["single", "shared_chip4"])
+@pytest.mark.parametrize("level", ["prep", "level 0", "level 1", "level 2", "level 3"])
+@pytest.mark.parametrize("h,w", UP_LATENTS)
+def test_upscale_unet_plan_launches_against_fp64(ctx, upscale_models, h, w, level, lanes):
+    """DDIMSampler._fast_sampling on the upscale model without guidance (bench.py upscale_secondary):
+    unet.plan(4, h, w, 86, 50, "sampler")."""
+    unet = upscale_models((h, w)).model.diffusion_model
+    build = lambda: unet.plan(UP_B, h, w, UP_NCTX, STEPS, "sampler")
+    plan = in_lanes(lanes, build)
+    assert (plan.B, plan.H, plan.W, plan.n_ctx, plan.rows, plan.arch.in_channels) == (UP_B, h, w, UP_NCTX, STEPS, 6)
+    known = variants(build()) if lanes > 1 else None
+    check_levels(ctx, plan, "upscale UNet %dx%d, %s" % (h, w, lanes_title(lanes)), upscale_unet_levels(h, w), level, lanes, known)
+
+
+@pytest.mark.parametrize("level", [0, 1, 2])
+def test_upscale_first_stage_decoder_plan_launches_against_fp64(ctx, upscale_models, level):
+    """LatentDiffusion.decode_first_stage of the upscale model: its kl-f4 decoder, 4 x 128x96 -> 512x384."""
+    m = upscale_models((128, 96))
+    plan = m.first_stage_model._decode_plan(UP_B, 128, 96, float(m.scale_factor))  # (decode_first_stage's sf)
+    assert plan.arch.factor == 4
+    levels = {k: (UP_B * 128 * 96 * 4 ** k,) for k in range(3)}
+    assert levels[2] == (786432,)
+    check_levels(ctx, plan, "upscale first-stage decoder 128x96", levels, level)
+
+
+@pytest.mark.parametrize("level", [0, 1, 2, 3])
+@pytest.mark.parametrize("H,W", [(256, 256), (256, 192)])
+def test_vae_encoder_plan_launches_against_fp64(ctx, model, H, W, level):
+    """AutoencoderKL.encode of the bbox model at B = 8 (encode_first_stage: img2img, edit_region, p_losses)."""
+    plan = model.first_stage_model._encode_plan(B, H, W)
+    levels = {k: (B * H * W // 4 ** k,) for k in range(4)}
+    check_levels(ctx, plan, "VAE encoder %dx%d" % (H, W), levels, level)
+
+
+def synth_stage(module, prefix):
+    from upgpt_amd import synth
+    module.load_state_dict({k: synth.synth_tensor(prefix + k, tuple(v.shape)) for k, v in module.state_dict().items()})
+    return module.cuda()
+
+
+@pytest.fixture(scope="module")
+def towers():
+    """The conditioning stages, on the recipe's weights under the checkpoint's names, built on first use:
+    'text' FrozenCLIPEmbedder, 'pooled' CLIPTextTower, 'image' FrozenClipImageEmbedder2, 'laion' CLIPTextImageCrossAtten."""
+    from upgpt_amd.clip_cross import CLIPTextImageCrossAtten
+    from upgpt_amd.clip_image import FrozenClipImageEmbedder2
+    from upgpt_amd.clip_text import CLIPTextTower, FrozenCLIPEmbedder
+    make = {"text": lambda: synth_stage(FrozenCLIPEmbedder(), "cond_stage_model."),
+            "pooled": lambda: synth_stage(CLIPTextTower(), "clip_text_encoder.model."),
+            "image": lambda: synth_stage(FrozenClipImageEmbedder2(), "extra_cond_models.0."),
+            "laion": lambda: synth_stage(CLIPTextImageCrossAtten(), "cond_stage_model.")}
+    made = {}
+
+    def get(name):
+        if name not in made:
+            made[name] = make[name]()
+        return made[name]
+
+    yield get
+    drop_plans(*made.values())
+    for m in made.values():  # (the laion stage keeps its tower objects outside the module tree)
+        for t in getattr(getattr(m, "model", None), "towers", ()):
+            drop_plans(t)
+    made.clear()
+    torch.cuda.empty_cache()
+
+
+def tower_plan(towers, which):
+    """(title, build) of a tower plan; build() is the call the product makes."""
+    if which == "text":  # FrozenCLIPEmbedder.encode_tokens -> CLIPTextTransformer._run -> _plan(B)
+        return "CLIP text tower B = 8 (hidden states)", lambda: towers("text").transformer._plan(B)
+    if which == "pooled":  # CLIPTextTower.encode_text -> _run -> _plan(n)
+        return "CLIP text tower B = 8 (pooled)", lambda: towers("pooled")._plan(B)
+    if which == "image":  # FrozenClipImageEmbedder2.forward -> encode_image -> CLIPVisual.forward -> _plan(b n)
+        return "CLIP image tower N = 72", lambda: towers("image").model.visual._plan(B * N_STYLES)
+    if which == "laion text":  # CLIPTextImageCrossAtten._plan: text_tower._plan(B) (hidden_act "gelu": plain fc1 launches)
+        return "laion text tower B = 8", lambda: towers("laion").model.text_tower._plan(B)
+    assert which == "laion image"  # CLIPTextImageCrossAtten._plan: vision_tower._plan(B n)
+    return "laion image tower N = 72", lambda: towers("laion").model.vision_tower._plan(B * N_STYLES)
+
+
+@pytest.mark.parametrize("which,lanes", [("text", 1), ("text", 4), ("pooled", 1), ("image", 1), ("image", 4), ("laion text", 1),
+                                         ("laion image", 1)])
+def test_clip_tower_plan_launches_against_fp64(ctx, towers, which, lanes):
+    title, build = tower_plan(towers, which)
+    plan, n = check_lowerings(ctx, build, title, lanes)
+    assert n == len(plan.convs)
+    f = [LR.fields(d) for d, _ in plan.convs]
+    qkv = [x for x in f if x["vt"]]
+    assert qkv and all(x["ln_colsum"] and x["vt_tokens"] % 32 for x in qkv)  # folded LayerNorm, V^T tail, odd token count
+    if which == "pooled":
+        assert (f[-1]["batch"], f[-1]["in_h"], f[-1]["in_w"]) == (B, 1, 1) and f[-1]["flags"] & L.F_OUT_F32
+    if "image" in which:
+        assert (qkv[0]["vt_tokens"], qkv[0]["vt_ld"], qkv[0]["vt_heads"], qkv[0]["vt_dhead"]) == (257, 288, 16, 64)
+        assert f[0]["c1"] == 608 and f[-1]["batch"] == B * N_STYLES
+    if which in ("text", "pooled", "image"):
+        assert any(x["ln_colsum"] and x["flags"] & L.F_QUICKGELU for x in f)
+
+
+def test_cross_stage_plan_launches_against_fp64(ctx, towers):
+    """CLIPTextImageCrossAtten._plan(8, 9): to_q over the 8 x 77 text rows, to_k | to_v over the 72 feature rows, to_out."""
+    text_plan, image_plan, plan = towers("laion")._plan(B, N_STYLES)
+    n = check_plan(ctx, plan, "cross stage B = 8, n = 9", 1)
+    assert n == len(plan.convs) == 3
+    assert sorted(rows_of(d) for d, _ in plan.convs) == [B * N_STYLES, B * 77, B * 77]
+    assert text_plan is towers("laion").model.text_tower._plan(B)  # (the towers' plans: the two laion cases above)
+    assert image_plan is towers("laion").model.vision_tower._plan(B * N_STYLES)
+
+
+@pytest.fixture(scope="module")
+def lpips_net():
+    from upgpt_amd import synth
+    from upgpt_amd.lpips import LPIPS
+    net = LPIPS()
+    net.load_state_dict(synth.synthetic_lpips_state(0))
+    net = net.cuda()
+    yield net
+    drop_plans(net)
+
+
+@pytest.mark.parametrize("H,W", LPIPS_SIZES)
+def test_lpips_plan_launches_against_fp64(ctx, lpips_net, H, W):
+    """LPIPS._layers -> _plan(pairs, h, w): per pair thirteen 3x3 launches at batch 2, none pinned (LpipsPlan never calls
+    apply_tuning): each keeps the SPLITK_MAX bound when the library splits it."""
+    plan = lpips_net._plan(1, H, W)
+    n = check_plan(ctx, plan, "LPIPS one pair of %dx%d" % (H, W), 1)
+    assert n == len(plan.convs) == 13
+    assert all(d.tune_cfg == 0 and d.batch == 2 and d.ksize == 3 for d, _ in plan.convs)
+
+
 # --------------------------------------------------- the branches of the harness that no plan takes with today's tables
 @pytest.mark.parametrize("hw,cin,cout,cap,want", [((64, 64), 64, 128, 64, "upk_groupnorm_finalize_f32"),
                                                   ((8, 8), 896, 896, 0, "y")])
 def test_harness_on_cost_model_launches(ctx, hw, cin, cout, cap, want):
-    """Every launch of the six plans is pinned by a table and none leaves more than 32 row blocks of GroupNorm partials, so
-    two hand-made descriptors take check_launch through what the plans leave idle: tune_cfg = 0 (the split-K factor read
-    off the kernel count) and gn_stats_cap > 32 followed by upk_groupnorm_finalize_f32.  The pointers only say 'set': the
-    replica replaces every one of them."""
+    """Every launch of the six headline plans is pinned by a table and none leaves more than 32 row blocks of GroupNorm
+    partials, so two hand-made descriptors take check_launch through what those plans leave idle: tune_cfg = 0 (the split-K
+    factor read off the kernel count) and gn_stats_cap > 32 followed by upk_groupnorm_finalize_f32.  (The upscale UNet's
+    level 0 and the LPIPS / cross-stage plans reach both by themselves; these two stay as the harness's own cases.)  The
+    pointers only say 'set': the replica replaces every one of them."""
     d = L.ConvDesc()
     d.x1 = d.w_packed = d.y = d.bias = d.gn_stats_ws = 1
     d.c1 = d.ld1 = cin

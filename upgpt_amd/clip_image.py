@@ -127,7 +127,6 @@ class _VisualPlan(Emitter):
         x = Act(self.alloc(N * S, d), N, S, 1, d)
         self._ln(P, tok, pk.vec(nm["ln_pre"] + ".weight"), pk.vec(nm["ln_pre"] + ".bias"), eps, x, N * S)
         vt_ld = _rup(S, 32)
-        fn_a = self.lib.upk_attention_f16
         M = N * S
         for i in range(cfg["layers"]):
             b = nm["layer"] % i
@@ -138,9 +137,9 @@ class _VisualPlan(Emitter):
             self.conv(P, x, wqkv, out=qk, ln_eps=eps,
                       vt=dict(t=vt, heads=heads, dhead=dh, ld=vt_ld, tokens=S, **{"from": 2 * d}))
             att = Act(self.alloc(M, d), N, S, 1, d)
-            aa = (qk.t.data_ptr(), 2 * d, S * 2 * d, qk.t[:, d:].data_ptr(), 2 * d, S * 2 * d, vt.data_ptr(), vt_ld,
-                  att.t.data_ptr(), d, S * d, N, heads, S, S, dh, float(dh ** -0.5))
-            P.add(lambda s, aa=aa: chk(fn_a(h, *aa, s)), qk, vt, att, cls="attention")
+            # (Emitter.attention: upk_attention_f16 with these seventeen arguments, and the launch recorded in P.attn)
+            self.attention(P, qk.t, 2 * d, S * 2 * d, qk.t[:, d:], 2 * d, S * 2 * d, vt, vt_ld, att.t, d, S * d, N, heads, S, S,
+                           dh, dh ** -0.5)
             x = self.conv(P, att, pk.pack(b + nm["out"]), residual=x)
             if erf_gelu:  # (hidden_act "gelu": a plain fc1 launch, then the exact GELU in place)
                 hmid = self.gelu(P, self.conv(P, x, pk.pack(b + nm["fc1"], ln=b + nm["ln2"]), ln_eps=eps))
