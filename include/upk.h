@@ -507,6 +507,20 @@ int upk_groupnorm_apply_nhwc_f16(upk_ctx* ctx, const void* x1, int c1, int ld1, 
                                  const float* beta, float eps, int fuse_silu, void* y, int ldy,
                                  const float* stats_ws, int stats_mode, int stats_nblk, int stats_ld,
                                  const float* stats_ws2, int stats_nblk2, int stats_ld2, upk_stream stream);
+/* Which kernels a GroupNorm call runs.  upk_groupnorm_num_paths() paths, named by upk_groupnorm_path_name ("?" outside):
+ * "onepass_v<V>n<NV>" = the one-launch kernel for feature maps of <= 64 pixels, a thread owning up to NV vectors of V
+ * channels of one group (V = the largest of 8 / 4 / 2 that divides the group width; an odd width has none), and
+ * "twopass" = the statistics pass and / or the apply pass.
+ * upk_groupnorm_plan: what upk_groupnorm_nhwc_f16 (with_stats = with_apply = 1), upk_groupnorm_stats_nhwc_f16
+ * (1, 0) or upk_groupnorm_apply_nhwc_f16 (0, 1) would run for these sizes: the launchers take their decision from the same
+ * function.  *nchunks / *pix_per_chunk: the layout [batch][*nchunks][groups][2] of the statistics workspace, chunk k
+ * holding the pixels [k, k + 1) * *pix_per_chunk (a one-pass path never touches the workspace); *apply_rows /
+ * *apply_blocks: pixels per workgroup and workgroups per sample of the apply pass (0 where none is launched).
+ * Nothing is enqueued; sizes the launch refuses are refused with the same code. */
+int upk_groupnorm_num_paths(void);
+const char* upk_groupnorm_path_name(int path);
+int upk_groupnorm_plan(upk_ctx* ctx, int c1, int c2, int batch, int hw, int groups, int with_stats, int with_apply,
+                       int* path, int* nchunks, int* pix_per_chunk, int* apply_rows, int* apply_blocks);
 
 /* LayerNorm over the last dim of fp16 [rows, d] (attention.py:203-205, eps 1e-5). */
 int upk_layernorm_f16(upk_ctx* ctx, const void* x, int ldx, int rows, int d, const float* gamma,

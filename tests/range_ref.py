@@ -416,7 +416,9 @@ def norm_input(shape, seed, s, chan_dim=-1, device="cpu"):
     return activations(shape, seed, s, mu=mu, sigma=sigma, device=device)
 
 
-GN_CASES = {"gn96": (96, 0), "gn64_32": (64, 32)}  # (c1, c2), 32 groups, hw 48, B 2
+# (c1, c2), 32 groups, hw 48, B 2.  Groups of 3 channels: NOT the one-launch kernel although hw <= 64 (it has no form for an
+# odd group width) but the statistics + apply pair with 2 pixels per chunk; tests/norm_ref.py has the tables per path
+GN_CASES = {"gn96": (96, 0), "gn64_32": (64, 32)}
 LN_ROWS = ((5, 1024), (33, 224))
 LNGEMM_CASES = {"ln96_224_256": (96, 224, 256, None), "ln50_448_512": (50, 448, 512, None),
                 "ln96_224_geglu": (96, 224, 512, "geglu")}

@@ -23,6 +23,7 @@ SYMBOLS = [
     "upk_conv_ln_rows",
     "upk_geglu_mlp_f16", "upk_geglu_mlp_supported", "upk_cross_block_f16", "upk_cross_block_supported", "upk_head_block_f16", "upk_head_block_supported",
     "upk_attention_f16", "upk_groupnorm_nhwc_f16", "upk_groupnorm_stats_nhwc_f16", "upk_groupnorm_chunks", "upk_groupnorm_apply_nhwc_f16", "upk_groupnorm_finalize_f32", "upk_groupnorm_ws_bytes",
+    "upk_groupnorm_num_paths", "upk_groupnorm_path_name", "upk_groupnorm_plan",
     "upk_layernorm_f16", "upk_timestep_embed_f16",
     "upk_nchw_f32_to_nhwc_f16", "upk_nhwc_f16_to_nchw_f32", "upk_f32_to_f16", "upk_ddim_step_f32",
     "upk_ddim_step_cfg_f32", "upk_ddim_step_edit_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_dpmpp_2m_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
@@ -197,6 +198,9 @@ def load_library(path=None):
             "upk_conv_gn_fused": (C.c_int, [vp, C.POINTER(ConvDesc), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
             "upk_groupnorm_finalize_f32": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
             "upk_groupnorm_ws_bytes": (C.c_size_t, [i32, i32]),
+            "upk_groupnorm_num_paths": (C.c_int, []),
+            "upk_groupnorm_path_name": (C.c_char_p, [i32]),
+            "upk_groupnorm_plan": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32] + [C.POINTER(C.c_int)] * 5),
             "upk_layernorm_f16": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, f32, vp, i32, vp]),
             "upk_timestep_embed_f16": (C.c_int, [vp, vp, i32, i32, f32, vp, i32, vp]),
             "upk_nchw_f32_to_nhwc_f16": (C.c_int, [vp, vp, i32, i32, i32, vp, i32, i32, i32, f32, vp]),
@@ -400,6 +404,19 @@ class Context:
 
     def groupnorm_ws_bytes(self, batch, hw):
         return self.lib.upk_groupnorm_ws_bytes(batch, hw)
+
+    def groupnorm_paths(self):
+        """Names of the GroupNorm paths, by index (upk_groupnorm_path_name)."""
+        return [self.lib.upk_groupnorm_path_name(i).decode() for i in range(self.lib.upk_groupnorm_num_paths())]
+
+    def groupnorm_plan(self, c1, c2, batch, hw, groups, with_stats=True, with_apply=True):
+        """-> dict(path=name, nchunks, pix_per_chunk, apply_rows, apply_blocks) of the GroupNorm call with these sizes
+        (upk_groupnorm_plan); enqueues nothing."""
+        o = [C.c_int(-1) for _ in range(5)]
+        self._chk(self.lib.upk_groupnorm_plan(self.h, c1, c2, batch, hw, groups, int(with_stats), int(with_apply),
+                                              *[C.byref(v) for v in o]))
+        return dict(path=self.lib.upk_groupnorm_path_name(o[0].value).decode(), nchunks=o[1].value,
+                    pix_per_chunk=o[2].value, apply_rows=o[3].value, apply_blocks=o[4].value)
 
     def layernorm(self, x, ldx, rows, d, gamma, beta, eps, y, ldy):
         self._chk(self.lib.upk_layernorm_f16(self.h, _ptr(x), ldx, rows, d, _ptr(gamma), _ptr(beta), eps,

@@ -467,6 +467,54 @@ extern "C" int upk_groupnorm_chunks(int hw) {
   return nch;
 }
 
+// What a GroupNorm call runs, decided in ONE place: the launchers and the query (upk_groupnorm_plan) both call gn_decide.
+enum { GN_V8N2 = 0, GN_V8N4, GN_V4N4, GN_V4N8, GN_V2N8, GN_TWOPASS, GN_NUM_PATHS };
+static const char* const kGnPathNames[GN_NUM_PATHS] = {"onepass_v8n2", "onepass_v8n4", "onepass_v4n4",
+                                                       "onepass_v4n8", "onepass_v2n8", "twopass"};
+
+struct GnPlan {
+  int path;                    // GN_*: a gn_onepass_kernel instantiation, or the statistics / apply pair
+  int nchunks, pix_per_chunk;  // layout of the statistics workspace (written by GN_TWOPASS with statistics only)
+  int rows, blocks;            // gn_apply_kernel: pixels per block, blocks per sample (0: no apply launch)
+};
+
+static int gn_decide(upk_ctx* ctx, int c1, int c2, int batch, int hw, int groups, bool with_stats, bool with_apply,
+                     GnPlan* p) {
+  const int C = c1 + c2;
+  if (c1 <= 0 || c2 < 0 || (c1 & 7) || (c2 & 7))
+    return upk_fail(ctx, UPK_EINVAL, "groupnorm: channels / leading dims must be multiples of 8");
+  if (groups <= 0 || groups > GN_GROUPS_MAX || C % groups || C > 2048)
+    return upk_fail(ctx, UPK_ESHAPE, "groupnorm: C=%d groups=%d unsupported", C, groups);
+  if (batch <= 0 || hw <= 0) return upk_fail(ctx, UPK_EINVAL, "groupnorm: empty");
+  if (!with_stats && !with_apply) return upk_fail(ctx, UPK_EINVAL, "groupnorm: neither statistics nor apply");
+  const int cpg = C / groups;
+  p->path = GN_TWOPASS;
+  p->rows = p->blocks = 0;
+  upk_gn_chunking(hw, &p->nchunks, &p->pix_per_chunk);
+  // small feature maps: statistics and normalisation in ONE launch (gn_onepass_kernel)
+  if (with_stats && with_apply && hw <= 64) {
+    const int v = !(cpg & 7) ? 8 : (!(cpg & 3) ? 4 : (!(cpg & 1) ? 2 : 0));
+    const int nv = v ? (hw * (cpg / v) + 255) / 256 : 0;
+    if (v == 8 && nv <= 2) p->path = GN_V8N2;
+    else if (v == 8 && nv <= 4) p->path = GN_V8N4;
+    else if (v == 4 && nv <= 4) p->path = GN_V4N4;
+    else if (v == 4 && nv <= 8) p->path = GN_V4N8;
+    else if (v == 2 && nv <= 8) p->path = GN_V2N8;
+    if (p->path != GN_TWOPASS) return UPK_OK;
+  }
+  if (!with_apply) return UPK_OK;
+  // apply: ~4 KB of fp16 per block (>= 3 blocks per CU on the UNet shapes: the kernel is a chain of
+  // dependent memory round trips, so it needs co-resident blocks, not long per-block loops)
+  // ... up to ~4096 blocks: beyond that (VAE decoder: 64 K - 524 K rows) a block's fixed part — folding the partial
+  // statistics, gamma / beta, the scale / shift table — outweighs its 4 KB of data
+  int rows = (2048 + C - 1) / C;
+  const long rows_big = ((long)hw * batch + 4095) / 4096;
+  if (rows_big > rows) rows = (int)(rows_big < 4096 ? rows_big : 4096);
+  p->rows = rows;
+  p->blocks = (hw + rows - 1) / rows;
+  return UPK_OK;
+}
+
 static int gn_launch(upk_ctx* ctx, const void* x1, int c1, int ld1, const void* x2, int c2, int ld2, int batch, int hw,
                      int groups, const float* gamma, const float* beta, float eps, int fuse_silu, void* y, int ldy,
                      float* stats_ws, upk_stream stream_, bool with_stats, int cp_nblk = 0, int cp_ld = 0,
@@ -475,12 +523,11 @@ static int gn_launch(upk_ctx* ctx, const void* x1, int c1, int ld1, const void* 
   if (!x1 || !stats_ws || (with_apply && (!gamma || !beta || !y)))
     return upk_fail(ctx, UPK_EINVAL, "groupnorm: null pointer");
   const int C = c1 + c2;
-  if (c1 <= 0 || c2 < 0 || (c1 & 7) || (c2 & 7) || (c2 && !x2) || (ld1 & 7) || (c2 && (ld2 & 7)) ||
-      (with_apply && (ldy & 7)))
+  if ((c2 > 0 && !x2) || (ld1 & 7) || (c2 > 0 && (ld2 & 7)) || (with_apply && (ldy & 7)))
     return upk_fail(ctx, UPK_EINVAL, "groupnorm: channels / leading dims must be multiples of 8");
-  if (groups <= 0 || groups > GN_GROUPS_MAX || C % groups || C > 2048)
-    return upk_fail(ctx, UPK_ESHAPE, "groupnorm: C=%d groups=%d unsupported", C, groups);
-  if (batch <= 0 || hw <= 0) return upk_fail(ctx, UPK_EINVAL, "groupnorm: empty");
+  GnPlan plan;
+  int rc = gn_decide(ctx, c1, c2, batch, hw, groups, with_stats, with_apply, &plan);
+  if (rc != UPK_OK) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   GnArgs a;
   a.x1 = (const f16*)x1;
@@ -492,7 +539,8 @@ static int gn_launch(upk_ctx* ctx, const void* x1, int c1, int ld1, const void* 
   a.hw = hw;
   a.groups = groups;
   a.cpg = C / groups;
-  upk_gn_chunking(hw, &a.nchunks, &a.pix_per_chunk);
+  a.nchunks = plan.nchunks;
+  a.pix_per_chunk = plan.pix_per_chunk;
   a.gamma = gamma;
   a.beta = beta;
   a.eps = eps;
@@ -510,36 +558,48 @@ static int gn_launch(upk_ctx* ctx, const void* x1, int c1, int ld1, const void* 
     return upk_fail(ctx, UPK_EINVAL, "groupnorm apply: channel partials need stats_ld >= channels and 0 < nblk <= %d for "
                     "every source", GN_MAX_CHUNKS);
   upk_prof_scope prof(ctx, UPK_CLS_GN, stream);
-  int rc = UPK_OK;
-  // small feature maps: statistics and normalisation in ONE launch (gn_onepass_kernel)
-  if (with_stats && with_apply && hw <= 64) {
-    const int v = !(a.cpg & 7) ? 8 : (!(a.cpg & 3) ? 4 : (!(a.cpg & 1) ? 2 : 0));
-    const int nv = v ? (hw * (a.cpg / v) + 255) / 256 : 0;
+  if (plan.path != GN_TWOPASS) {
     const dim3 grid(groups, batch);
-    bool done = true;
-    if (v == 8 && nv <= 2) hipLaunchKernelGGL((gn_onepass_kernel<8, 2>), grid, dim3(256), 0, stream, a);
-    else if (v == 8 && nv <= 4) hipLaunchKernelGGL((gn_onepass_kernel<8, 4>), grid, dim3(256), 0, stream, a);
-    else if (v == 4 && nv <= 4) hipLaunchKernelGGL((gn_onepass_kernel<4, 4>), grid, dim3(256), 0, stream, a);
-    else if (v == 4 && nv <= 8) hipLaunchKernelGGL((gn_onepass_kernel<4, 8>), grid, dim3(256), 0, stream, a);
-    else if (v == 2 && nv <= 8) hipLaunchKernelGGL((gn_onepass_kernel<2, 8>), grid, dim3(256), 0, stream, a);
-    else done = false;
-    if (done) return upk_check_launch(ctx, "gn_onepass");
+    switch (plan.path) {
+      case GN_V8N2: hipLaunchKernelGGL((gn_onepass_kernel<8, 2>), grid, dim3(256), 0, stream, a); break;
+      case GN_V8N4: hipLaunchKernelGGL((gn_onepass_kernel<8, 4>), grid, dim3(256), 0, stream, a); break;
+      case GN_V4N4: hipLaunchKernelGGL((gn_onepass_kernel<4, 4>), grid, dim3(256), 0, stream, a); break;
+      case GN_V4N8: hipLaunchKernelGGL((gn_onepass_kernel<4, 8>), grid, dim3(256), 0, stream, a); break;
+      default: hipLaunchKernelGGL((gn_onepass_kernel<2, 8>), grid, dim3(256), 0, stream, a); break;
+    }
+    return upk_check_launch(ctx, "gn_onepass");
   }
   if (with_stats) {
     hipLaunchKernelGGL(gn_stats_kernel, dim3(a.nchunks, batch), dim3(256), 0, stream, a);
     rc = upk_check_launch(ctx, "gn_stats");
     if (rc || !with_apply) return rc;
   }
-  // apply: ~4 KB of fp16 per block (>= 3 blocks per CU on the UNet shapes: the kernel is a chain of
-  // dependent memory round trips, so it needs co-resident blocks, not long per-block loops)
-  // ... up to ~4096 blocks: beyond that (VAE decoder: 64 K - 524 K rows) a block's fixed part — folding the partial
-  // statistics, gamma / beta, the scale / shift table — outweighs its 4 KB of data
-  int rows = (2048 + C - 1) / C;
-  const long rows_big = ((long)hw * batch + 4095) / 4096;
-  if (rows_big > rows) rows = (int)(rows_big < 4096 ? rows_big : 4096);
-  const int blocks = (hw + rows - 1) / rows;
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(blocks, batch), dim3(256), (size_t)C * 2 * sizeof(float), stream, a, rows);
+  hipLaunchKernelGGL(gn_apply_kernel, dim3(plan.blocks, batch), dim3(256), (size_t)C * 2 * sizeof(float), stream, a,
+                     plan.rows);
   return upk_check_launch(ctx, "gn_apply");
+}
+
+extern "C" int upk_groupnorm_num_paths(void) { return GN_NUM_PATHS; }
+
+extern "C" const char* upk_groupnorm_path_name(int path) {
+  return (path >= 0 && path < GN_NUM_PATHS) ? kGnPathNames[path] : "?";
+}
+
+extern "C" int upk_groupnorm_plan(upk_ctx* ctx, int c1, int c2, int batch, int hw, int groups, int with_stats,
+                                  int with_apply, int* path, int* nchunks, int* pix_per_chunk, int* apply_rows,
+                                  int* apply_blocks) {
+  if (!ctx) return UPK_EINVAL;
+  if (!path || !nchunks || !pix_per_chunk || !apply_rows || !apply_blocks)
+    return upk_fail(ctx, UPK_EINVAL, "groupnorm_plan: null result pointer");
+  GnPlan plan;
+  const int rc = gn_decide(ctx, c1, c2, batch, hw, groups, with_stats != 0, with_apply != 0, &plan);
+  if (rc != UPK_OK) return rc;
+  *path = plan.path;
+  *nchunks = plan.nchunks;
+  *pix_per_chunk = plan.pix_per_chunk;
+  *apply_rows = plan.rows;
+  *apply_blocks = plan.blocks;
+  return UPK_OK;
 }
 
 extern "C" int upk_groupnorm_nhwc_f16(upk_ctx* ctx, const void* x1, int c1, int ld1, const void* x2, int c2, int ld2,
