@@ -1,8 +1,10 @@
 """GPU debug: product UNet forward vs the CPU oracle, per block (dev tool)."""
 import sys, time
 import torch
-import os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import upgpt_amd
+from block_ref import taps_nchw
 from upgpt_amd import synth
 from oracle import unet as o_unet
 
@@ -27,8 +29,10 @@ out = unet(x.cuda(), t.cuda(), context=inp["c_crossattn"].cuda())
 torch.cuda.synchronize()
 print("hip first call %.2fs" % (time.time() - t0))
 pl = unet.plan(B, 32, 24, ntok, B, "forward")
-for name, act in pl.taps.items():
-    got = act.t[:, :act.C].float().reshape(act.B, act.H, act.W, act.C).permute(0, 3, 1, 2).cpu()
+for name, got in taps_nchw(pl).items():
+    if name == "eps":
+        continue
+    got = got.float().cpu()
     r = taps[name]
     err = (got - r).abs().max().item()
     print("%-18s shape %-22s max|ref| %8.3f  max err %9.5f  rel %.2e" % (name, tuple(r.shape), r.abs().max(), err, err / r.abs().max()))
