@@ -436,14 +436,13 @@ constexpr int kNumAsCfgs = sizeof(kAsCfgs) / sizeof(kAsCfgs[0]);
 
 int astat_num_configs() { return kNumAsCfgs; }
 const char* astat_config_name(int c) { return (c >= 0 && c < kNumAsCfgs) ? kAsCfgs[c].name : "?"; }
-int astat_config_ni(int c) { return (c >= 0 && c < kNumAsCfgs) ? kAsCfgs[c].ni : 0; }
 
-// Geometry of configuration `c` for the launch in `a` (filled by conv_impl): false = outside the family's domain.
-// ppw_req: output-column passes per workgroup (0 = enough workgroups to fill the chip once).
+// Geometry of configuration `c` for the launch in `a` (filled by conv_plan): false = outside the family's domain.
+// ppw_req: output-column passes per workgroup (0 = enough workgroups to fill the chip once; more than there are: false).
 bool astat_plan(const upk_ctx* ctx, const IgemmArgs& a, int c, int ppw_req, AsPlan* pl) {
   if (c < 0 || c >= kNumAsCfgs) return false;
   const AsCfg& k = kAsCfgs[c];
-  if (!a.linear || a.ph_on || a.partial) return false;
+  if (!a.linear || a.ph_on) return false;
   if (a.nchunks < k.pf || a.nchunks % k.pf) return false;
   if (a.npad % (k.ni * 16)) return false;  // (a wave's NI fragments are addressed off one base: all in range or none)
   const bool geglu = a.flags & UPK_F_GEGLU;
@@ -456,6 +455,7 @@ bool astat_plan(const upk_ctx* ctx, const IgemmArgs& a, int c, int ppw_req, AsPl
   if (lds > 160 * 1024) return false;
   pl->bm = BM;
   pl->pw = PW;
+  pl->ni = k.ni;
   pl->lds_bytes = (int)lds;
   pl->npass = (a.npad + PW - 1) / PW;
   pl->tiles_m = (a.M + BM - 1) / BM;
@@ -465,7 +465,7 @@ bool astat_plan(const upk_ctx* ctx, const IgemmArgs& a, int c, int ppw_req, AsPl
     const int tn = want_n < pl->npass ? (want_n < 1 ? 1 : want_n) : pl->npass;
     ppw = (pl->npass + tn - 1) / tn;
   }
-  if (ppw > pl->npass) ppw = pl->npass;
+  if (ppw > pl->npass) return false;
   pl->ppw = ppw;
   pl->tiles_n = (pl->npass + ppw - 1) / ppw;
   pl->lds_bytes += 2 * ppw * PW * 4;  // bias | column sums of the workgroup's columns
@@ -473,15 +473,13 @@ bool astat_plan(const upk_ctx* ctx, const IgemmArgs& a, int c, int ppw_req, AsPl
   return true;
 }
 
-int astat_launch(upk_ctx* ctx, IgemmArgs& a, int c, const AsPlan& pl, dim3 grid, hipStream_t stream) {
+int astat_launch(upk_ctx* ctx, const IgemmArgs& a, int c, const AsPlan& pl, dim3 grid, dim3 block, hipStream_t stream) {
   const AsCfg& k = kAsCfgs[c];
   static unsigned long long attr_set[kNumAsCfgs][2] = {};
   if (int rc = upk_lds_attr_once(ctx, (const void*)k.fn, &attr_set[c][0])) return rc;
   if (int rc = upk_lds_attr_once(ctx, (const void*)k.fn_gen, &attr_set[c][1])) return rc;
   const bool geglu = a.flags & UPK_F_GEGLU;
   const bool fast = geglu ? Epi::plain_geglu(a) : (Epi::plain(a) && !a.gn_cp && !a.lnr_out && !a.rowvec);
-  a.as_ppw = pl.ppw;
-  a.as_npass = pl.npass;
   AsArgs s;
   memset(&s, 0, sizeof(s));
   s.x1 = a.x1, s.x2 = a.x2, s.x3 = a.x3, s.x4 = a.x4, s.w = a.w, s.zero = a.zero, s.bias = a.bias, s.res = a.res;
@@ -492,7 +490,7 @@ int astat_launch(upk_ctx* ctx, IgemmArgs& a, int c, const AsPlan& pl, dim3 grid,
   s.ppw = pl.ppw, s.npass = pl.npass;
   s.tiles_m = a.tiles_m, s.tiles_n = a.tiles_n, s.xm_pm = a.xm_pm, s.xm_pn = a.xm_pn, s.xm_mi = a.xm_mi, s.xm_nj = a.xm_nj;
   s.lnr_slots = a.lnr_slots, s.ln_inv_dim = a.ln_inv_dim, s.ln_eps = a.ln_eps;
-  hipLaunchKernelGGL(fast ? k.fn : k.fn_gen, grid, dim3(512), (size_t)pl.lds_bytes, stream, s, a);
+  hipLaunchKernelGGL(fast ? k.fn : k.fn_gen, grid, block, (size_t)pl.lds_bytes, stream, s, a);
   return upk_check_launch(ctx, "igemm_as");
 }
 

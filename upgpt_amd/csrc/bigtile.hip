@@ -409,21 +409,23 @@ constexpr int kNumBt = sizeof(kBt) / sizeof(kBt[0]);
 
 int bt_num_configs() { return kNumBt; }
 const char* bt_config_name(int c) { return (c >= 0 && c < kNumBt) ? kBt[c].name : "?"; }
-bool bt_full_epilogue(int c) { return c >= 0 && c < kNumBt && kBt[c].fn_fe != nullptr; }
-void bt_tile(int c, int* bm, int* bn, int* occ, int* mi, int* ni, int* wn) {
-  if (c < 0 || c >= kNumBt) c = 0;  // (callers range-check; never index past the table)
-  *wn = kBt[c].wn;
-  *bm = kBt[c].mi * 16 * kBt[c].wm;
-  *bn = kBt[c].ni * 16 * kBt[c].wn;
-  *occ = kBt[c].wm * kBt[c].wn == 4 ? 2 : 1;
-  *mi = kBt[c].mi;
-  *ni = kBt[c].ni;
+
+// Geometry of configuration `c`; false = the launch in `a` (filled by conv_plan) at split-K factor `splitk` is outside the
+// family's domain: an appended K segment, a fragment-side LayerNorm fold, an epilogue that is not plain where K is not
+// split and the configuration has no general-epilogue instantiation, GEGLU on waves narrower than 64 columns
+bool bt_plan(const upk_ctx* ctx, const IgemmArgs& a, int c, int splitk, BtPlan* pl) {
+  if (c < 0 || c >= kNumBt) return false;
+  const BtCfg& k = kBt[c];
+  *pl = {k.mi * 16 * k.wm, k.ni * 16 * k.wn, k.wm * k.wn == 4 ? 2 : 1, k.mi, k.ni, k.wn, k.wm * k.wn * 64};
+  if (a.x3 || (a.ln_u && !a.lnr_in) || !splitk_fits(ctx, a, splitk)) return false;
+  if (splitk == 1 && !Epi::plain(a) && !k.fn_fe) return false;
+  return !(a.flags & UPK_F_GEGLU) || (k.ni * 16) % 64 == 0;
 }
-int bt_launch(upk_ctx* ctx, const IgemmArgs& a, int c, dim3 grid, hipStream_t stream) {
+int bt_launch(upk_ctx* ctx, const IgemmArgs& a, int c, dim3 grid, dim3 block, hipStream_t stream) {
   // (split launches write partial slabs: no epilogue in the kernel)
   const bool fe = !a.partial && !Epi::plain(a);
   if (fe && !kBt[c].fn_fe) return upk_fail(ctx, UPK_ESHAPE, "conv: %s has no general-epilogue instantiation", kBt[c].name);
-  hipLaunchKernelGGL(fe ? kBt[c].fn_fe : kBt[c].fn, grid, dim3(kBt[c].wm * kBt[c].wn * 64), 0, stream, a);
+  hipLaunchKernelGGL(fe ? kBt[c].fn_fe : kBt[c].fn, grid, block, 0, stream, a);
   return upk_check_launch(ctx, "igemm_bt");
 }
 

@@ -1170,6 +1170,7 @@ const CfgInfo kCfgs[] = {
     // 128 accumulator registers + the plain / statistics epilogues spill 50-200 VGPRs at 2 waves per SIMD; not kept)
 };
 constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
+constexpr int kSplitKs[] = {1, 2, 3, 4, 6, 8, 9, 12, 16, 18};  // split-K candidates of the cost model and of the autotuner
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
@@ -1230,13 +1231,27 @@ extern "C" int upk_conv_override(upk_ctx* ctx, int cfg, int splitk) {
   return UPK_OK;
 }
 
-// launch == false: stops after the (config, split-K) decision and reports whether the reduce pass will
-// produce GroupNorm partials (upk_conv_gn_fused)
-static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, bool launch, int* gn_fused,
-                     int* gn_nblk = nullptr, int* lnr_slots = nullptr) {
-  if (lnr_slots) *lnr_slots = 0;
-  if (!ctx || !d) return UPK_EINVAL;
-  hipStream_t stream = (hipStream_t)stream_;
+// ---- A launch is planned, then launched.  conv_plan decides everything and touches no device: of the
+// context it reads num_cus, ws, ws_bytes and zero_page and writes err.  conv_launch enqueues what the plan says; the
+// queries (upk_conv_gn_fused, upk_conv_ln_rows) and the autotuner read the same plan.
+enum { FAM_RING, FAM_ASTAT, FAM_BIGTILE };  // kCfgs (register-staged / DMA ring) | astat.hip | bigtile.hip
+enum { RED_NONE, RED_PLAIN, RED_GN_PARTIALS, RED_GN_APPLY };  // the pass behind a split-K launch
+struct ConvPlan {
+  IgemmArgs a;
+  int family, cfg;  // cfg: index in the family's own table
+  int zdim, nph;    // K splits (grid.z), upsample phases (grid.y)
+  int bm;           // rows of an M tile
+  dim3 grid, block;
+  AsPlan as;  // FAM_ASTAT
+  BtPlan bt;  // FAM_BIGTILE
+  int reduce, ga_nv;  // RED_GN_APPLY: vectors of 4 channels per thread
+  int gn_mode, gn_nblk, lnr_slots;  // by-products, as upk_conv_gn_fused / upk_conv_ln_rows report them
+};
+inline int family_base(int f) { return f == FAM_RING ? 0 : kNumCfgs + (f == FAM_BIGTILE ? astat_num_configs() : 0); }
+
+// Plan step 1: check the descriptor and translate it into the kernels' arguments (phase form, appended K segment,
+// folded LayerNorm)
+static int conv_translate(upk_ctx* ctx, const upk_conv_desc* d, IgemmArgs& a) {
   if (!d->x1 || !d->w_packed || !d->y) return upk_fail(ctx, UPK_EINVAL, "conv: null x1/w/y");
   if (d->c1 <= 0 || (d->c1 & 31) || (d->c2 & 31) || d->c2 < 0)
     return upk_fail(ctx, UPK_ESHAPE, "conv: channels must be multiples of 32 (c1=%d c2=%d)", d->c1, d->c2);
@@ -1251,7 +1266,6 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
   if (!(flags & UPK_F_OUT_NCHW_F32) && (d->ldy & 3)) return upk_fail(ctx, UPK_EINVAL, "conv: ldy %% 4");
   if (d->residual && (d->ld_res & 3)) return upk_fail(ctx, UPK_EINVAL, "conv: ld_res %% 4");
 
-  IgemmArgs a;
   memset(&a, 0, sizeof(a));
   a.x1 = (const f16*)d->x1;
   a.x2 = (const f16*)d->x2;
@@ -1290,8 +1304,6 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
   a.WL = a.ups ? 2 * a.WS : a.WS;
   a.ks = d->ksize;
   a.stride = d->stride;
-  a.ph_on = 0;
-  a.ph_wstride = 0;
   const bool phases = d->w_phase && a.ups && d->ksize == 3 && d->stride == 1 && !(flags & UPK_F_PAD_ASYM) &&
                       !d->x3 && !d->ln_colsum && !d->vt && !d->residual && !d->rowvec &&
                       !(flags & (UPK_F_GEGLU | UPK_F_OUT_NCHW_F32));
@@ -1333,7 +1345,6 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
   a.ln_u = d->ln_colsum;
   a.ln_eps = d->ln_eps;
   a.ln_inv_dim = d->ln_dim > 0 ? 1.0f / (float)d->ln_dim : 0.f;
-  a.lnr_out = nullptr;
   a.lnr_in = a.ln_u ? d->ln_rows_in : nullptr;
   a.lnr_slots = d->ln_rows_slots;
   if (a.lnr_in && (a.lnr_slots < 1 || a.lnr_slots > 8))
@@ -1363,96 +1374,86 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
   if (const char* ab = getenv("UPK_ABLATE")) a.flags |= (int)strtol(ab, nullptr, 0) & 0xFFF0000;
 #endif
   a.dbg = (unsigned long long*)((char*)ctx->ws + ctx->ws_bytes - 4096);
+  return UPK_OK;
+}
 
-  // ---- choose config + split-K ----
-  int best = -1, best_sk = 1;
-  double best_t = 1e30;
-  const int sk_cands[] = {1, 2, 3, 4, 6, 8, 9, 12, 16, 18};
-  const int nph = a.ph_on ? 4 : 1;
-  const size_t slab = (size_t)a.M * a.npad * sizeof(slab_t) * nph;
-  const int want_cfg = ctx->cfg_override >= 0 ? ctx->cfg_override : (d->tune_cfg > 0 ? d->tune_cfg - 1 : -1);
-  const int want_sk = ctx->splitk_override > 0 ? ctx->splitk_override : (d->tune_splitk > 0 ? d->tune_splitk : 0);
+// Plan step 2: family, configuration and split-K factor — what the request (want_cfg, want_sk) names, an error if that
+// does not fit, the cost model's choice where it names nothing — and the tiling that follows from them
+static int conv_pick(upk_ctx* ctx, ConvPlan& p, int want_cfg, int want_sk) {
+  IgemmArgs& a = p.a;
+  const bool geglu = a.flags & UPK_F_GEGLU;
   if (want_cfg >= upk_conv_num_configs())
     return upk_fail(ctx, UPK_ESHAPE, "conv: configuration index %d out of range (%d configurations; stale tuning file?)", want_cfg,
                     upk_conv_num_configs());
-  AsPlan aspl;
-  const int bt0 = kNumCfgs + astat_num_configs();
-  const bool bt_able = !a.x3 && !(a.ln_u && !a.lnr_in);  // (no appended segment, no fragment-side LayerNorm fold)
-  bool is_bt = want_cfg >= bt0;
-  int bt_bm = 0, bt_bn = 0, bt_occ = 1, bt_mi = 0, bt_ni = 0, bt_wn = 1;
-  if (is_bt) {
-    bt_tile(want_cfg - bt0, &bt_bm, &bt_bn, &bt_occ, &bt_mi, &bt_ni, &bt_wn);
-    const int sk = want_sk > 0 ? want_sk : 1;
-    if (!bt_able || (sk == 1 && !Epi::plain(a) && !bt_full_epilogue(want_cfg - bt0)) || (geglu && ((bt_ni * 16) % 64 != 0)) ||
-        (a.ln_u && sk > 1) || (sk > 1 && (slab * sk > ctx->ws_bytes || a.nchunks / sk < 4)))
-      return upk_fail(ctx, UPK_ESHAPE, "conv: big-tile configuration %s (split-K %d) does not fit this launch",
-                      bt_config_name(want_cfg - bt0), sk);
-    best = want_cfg;
-    best_sk = sk;
-  }
-  const bool is_as = want_cfg >= kNumCfgs && !is_bt;
-  if (is_as) {
-    if (!astat_plan(ctx, a, want_cfg - kNumCfgs, want_sk, &aspl) || (want_sk > 1 && want_sk > aspl.npass))
+  p.family = want_cfg >= family_base(FAM_BIGTILE) ? FAM_BIGTILE : (want_cfg >= family_base(FAM_ASTAT) ? FAM_ASTAT : FAM_RING);
+  p.cfg = want_cfg - family_base(p.family);
+  int sk = 1;
+  if (p.family == FAM_BIGTILE) {
+    sk = want_sk > 0 ? want_sk : 1;
+    if (!bt_plan(ctx, a, p.cfg, sk, &p.bt))
+      return upk_fail(ctx, UPK_ESHAPE, "conv: big-tile configuration %s (split-K %d) does not fit this launch", bt_config_name(p.cfg), sk);
+  } else if (p.family == FAM_ASTAT) {
+    if (!astat_plan(ctx, a, p.cfg, want_sk, &p.as))
       return upk_fail(ctx, UPK_ESHAPE, "conv: A-stationary configuration %s (passes per workgroup %d) does not fit this launch",
-                      astat_config_name(want_cfg - kNumCfgs), want_sk);
-    best = want_cfg;
-    best_sk = 1;
-  }
-  for (int c = 0; c < kNumCfgs && !is_as && !is_bt; ++c) {
-    if (want_cfg >= 0 && c != want_cfg) continue;
-    // folded LayerNorm: row statistics come from the M x N-split wave-specialised kernels, whole K in one block
-    if (a.ln_u && !a.lnr_in && !kCfgs[c].fn_ln) continue;
-    if (a.x3 && !kCfgs[c].fn_app) continue;  // the appended K segment lives in the wave-specialised loader
-    for (int sk : sk_cands) {
-      if (want_sk > 0 && sk != want_sk) continue;
-      if (a.ln_u && sk > 1) continue;
-      if (sk > 1 && (slab * sk > ctx->ws_bytes || a.nchunks / sk < 4)) continue;
-      const double t = estimate(kCfgs[c], a.M * nph, a.npad, a.nchunks, sk, ctx->num_cus, geglu);
-      if (t < best_t) {
-        best_t = t;
-        best = c;
-        best_sk = sk;
+                      astat_config_name(p.cfg), want_sk);
+  } else {
+    p.cfg = -1;
+    double best_t = 1e30;
+    for (int c = 0; c < kNumCfgs; ++c) {
+      if (want_cfg >= 0 && c != want_cfg) continue;
+      // folded LayerNorm: row statistics come from the M x N-split wave-specialised kernels, whole K in one block
+      if (a.ln_u && !a.lnr_in && !kCfgs[c].fn_ln) continue;
+      if (a.x3 && !kCfgs[c].fn_app) continue;  // the appended K segment lives in the wave-specialised loader
+      for (int s : kSplitKs) {
+        if ((want_sk > 0 && s != want_sk) || !splitk_fits(ctx, a, s)) continue;
+        const double t = estimate(kCfgs[c], a.M * p.nph, a.npad, a.nchunks, s, ctx->num_cus, geglu);
+        if (t < best_t) best_t = t, p.cfg = c, sk = s;
       }
     }
-  }
-  if (want_cfg < 0 && want_sk <= 1 && bt_able && Epi::plain(a) && best >= 0 && best_sk == 1) {
-    // cost model for the big-tile family: MFMA-bound stages (16 cycles per fragment MFMA, four SIMDs in parallel, the
-    // workgroups of a CU taking turns) + prologue / epilogue per tile; only where every CU gets a tile
-    for (int c = 0; c < bt_num_configs(); ++c) {
-      int bm, bn, occ, mi, ni, wn;
-      bt_tile(c, &bm, &bn, &occ, &mi, &ni, &wn);
-      if (geglu && ((ni * 16) % 64 != 0)) continue;
-      const long tiles = (long)cdiv(a.M, bm) * cdiv(a.npad, bn) * nph;
-      if (tiles < ctx->num_cus) continue;
-      const double rounds = ceil((double)tiles / ((double)ctx->num_cus * occ));
-      const double t = rounds * occ * ((double)a.nchunks * (mi * ni * 16.0 * 1.2 + 60.0) + 9000.0);
-      if (t < best_t) {
-        best_t = t;
-        best = bt0 + c;
-        best_sk = 1;
-        is_bt = true;
-        bt_bm = bm, bt_bn = bn, bt_occ = occ, bt_mi = mi, bt_ni = ni, bt_wn = wn;
+    if (want_cfg < 0 && want_sk <= 1 && Epi::plain(a) && p.cfg >= 0 && sk == 1) {
+      // cost model for the big-tile family: MFMA-bound stages (16 cycles per fragment MFMA, four SIMDs in parallel, the
+      // workgroups of a CU taking turns) + prologue / epilogue per tile; only where every CU gets a tile
+      for (int c = 0; c < bt_num_configs(); ++c) {
+        BtPlan bt;
+        if (!bt_plan(ctx, a, c, 1, &bt)) continue;
+        const long tiles = (long)cdiv(a.M, bt.bm) * cdiv(a.npad, bt.bn) * p.nph;
+        if (tiles < ctx->num_cus) continue;
+        const double rounds = ceil((double)tiles / ((double)ctx->num_cus * bt.occ));
+        const double t = rounds * bt.occ * ((double)a.nchunks * (bt.mi * bt.ni * 16.0 * 1.2 + 60.0) + 9000.0);
+        if (t < best_t) best_t = t, p.family = FAM_BIGTILE, p.cfg = c, p.bt = bt;
       }
     }
+    if (p.cfg < 0) {
+      if (want_sk > 1 && slab_bytes(a) * want_sk > ctx->ws_bytes)
+        return upk_fail(ctx, UPK_EWORKSPACE, "conv: split-K %d needs %zu workspace bytes, have %zu", want_sk,
+                        slab_bytes(a) * want_sk, ctx->ws_bytes);
+      return upk_fail(ctx, UPK_ESHAPE, "conv: no kernel configuration fits (geglu=%d)", (int)geglu);
+    }
   }
-  if (best < 0) {
-    if (want_sk > 1 && slab * want_sk > ctx->ws_bytes)
-      return upk_fail(ctx, UPK_EWORKSPACE, "conv: split-K %d needs %zu workspace bytes, have %zu", want_sk,
-                      slab * want_sk, ctx->ws_bytes);
-    return upk_fail(ctx, UPK_ESHAPE, "conv: no kernel configuration fits (geglu=%d)", (int)geglu);
+  if (p.family == FAM_BIGTILE) {
+    p.bm = p.bt.bm, a.tiles_n = cdiv(a.npad, p.bt.bn), p.block = dim3(p.bt.threads);
+  } else if (p.family == FAM_ASTAT) {
+    p.bm = p.as.bm, a.tiles_n = p.as.tiles_n, a.as_ppw = p.as.ppw, a.as_npass = p.as.npass, p.block = dim3(512);
+  } else {
+    const CfgInfo& c = kCfgs[p.cfg];
+    p.bm = c.mi * 16 * c.wm, a.tiles_n = cdiv(a.npad, c.ni * 16 * c.wn), p.block = dim3(c.nbuf ? 512 : c.wm * c.wn * 64);
   }
-  const CfgInfo& c = kCfgs[(is_as || is_bt) ? 0 : best];  // (not used by the A-stationary / big-tile families beyond this block)
-  const int BM = is_bt ? bt_bm : (is_as ? aspl.bm : c.mi * 16 * c.wm);
-  const int BN = is_bt ? bt_bn : (is_as ? aspl.pw * aspl.ppw : c.ni * 16 * c.wn);
-  a.tiles_m = cdiv(a.M, BM);
-  a.tiles_n = is_as ? aspl.tiles_n : cdiv(a.npad, BN);
-  a.chunks_per_split = cdiv(a.nchunks, best_sk);
-  const int zdim = cdiv(a.nchunks, a.chunks_per_split);
-  a.partial = (zdim > 1) ? (float*)ctx->ws : nullptr;
+  a.tiles_m = cdiv(a.M, p.bm);
+  a.chunks_per_split = cdiv(a.nchunks, sk);
+  p.zdim = cdiv(a.nchunks, a.chunks_per_split);
+  a.partial = (p.zdim > 1) ? (float*)ctx->ws : nullptr;
+  return UPK_OK;
+}
+
+// Plan step 3: what the launch leaves besides its output — the GroupNorm of the output (modes 0-3 of upk_conv_gn_fused)
+// and the LayerNorm row sums (slots of upk_conv_ln_rows) — and with it the kind of reduce pass
+static void conv_byproducts(ConvPlan& p, const upk_conv_desc* d) {
+  IgemmArgs& a = p.a;
+  const int zdim = p.zdim, BM = p.bm;
   // GroupNorm partials from the reduce pass (see igemm_reduce_gn_kernel)
   // ... or the whole GroupNorm from the reduce pass (igemm_reduce_gnapply_kernel)
   bool gn_apply = false;
-  int ga_nv = 0;
+  p.ga_nv = 0;
   if (d->gno_y && !a.ph_on && zdim > 1 && Epi::plain(a) && d->gn_groups > 0 && a.n_out % d->gn_groups == 0 && d->gno_gamma &&
       d->gno_beta) {
     const int cpg = a.n_out / d->gn_groups;
@@ -1462,7 +1463,7 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
     const bool v4 = !(cpg & 3) && !(a.ldy & 3) && !(d->gno_ld & 3) && (!a.res || !(a.ldr & 3));
     const long nvec = (long)a.Ho * a.Wo * (cpg / 4);
     const int nv = (int)((nvec + 255) / 256);
-    if (v4 && nv <= 2) gn_apply = true, ga_nv = nv;  // (the instantiations below: <4, 1>, <4, 2>)
+    if (v4 && nv <= 2) gn_apply = true, p.ga_nv = nv;  // (the instantiations of conv_launch: <4, 1>, <4, 2>)
   }
   const bool gn_fuse = !gn_apply && !a.ph_on && d->gn_stats_ws && zdim > 1 && Epi::plain(a) && !(a.n_out & 7) && a.n_out <= 2048 &&
                        d->gn_groups > 0 && d->gn_groups <= UPK_GN_GROUPS_MAX && a.n_out % d->gn_groups == 0 &&
@@ -1479,41 +1480,33 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
     a.gn_hw = hw_out;
   }
   // LayerNorm row sums of the output for the consumer GEMM (Epi::tile_plain_lnr / the K-split kernels' epilogue)
-  if (d->ln_rows_out && !a.ph_on && zdim == 1 && Epi::plain(a) && !gn_cp && (is_as || is_bt || c.wm * c.wn > 1 || c.nbuf > 0)) {
-    // (K-split kernels: one slot per N tile; A-stationary: one per 16 * NI columns of its single pass, else none)
-    const int slots = is_as ? (aspl.npass == 1 ? cdiv(a.npad, astat_config_ni(best - kNumCfgs) * 16) : 99)
-                            : a.tiles_n * (is_bt ? bt_wn : c.wn);
+  p.lnr_slots = 0;
+  if (d->ln_rows_out && !a.ph_on && zdim == 1 && Epi::plain(a) && !gn_cp) {
+    // (K-split kernels: one slot per N tile; A-stationary: one per 16 * NI columns of its single pass, else none; the
+    // classic one-wave kernels: none)
+    int slots = 99;
+    if (p.family == FAM_ASTAT) slots = p.as.npass == 1 ? cdiv(a.npad, p.as.ni * 16) : 99;
+    else if (p.family == FAM_BIGTILE) slots = a.tiles_n * p.bt.wn;
+    else if (kCfgs[p.cfg].wm * kCfgs[p.cfg].wn > 1 || kCfgs[p.cfg].nbuf > 0) slots = a.tiles_n * kCfgs[p.cfg].wn;
     if (slots <= 8) {
       a.lnr_out = d->ln_rows_out;
-      if (lnr_slots) *lnr_slots = slots;
+      p.lnr_slots = slots;
     }
   }
-  if (gn_fused) *gn_fused = gn_apply ? 3 : (gn_fuse ? 1 : (gn_cp ? 2 : 0));
-  if (gn_nblk) *gn_nblk = gn_cp ? a.gn_nblk : 0;
-  if (!launch) return UPK_OK;
+  p.gn_mode = gn_apply ? 3 : (gn_fuse ? 1 : (gn_cp ? 2 : 0));
+  p.gn_nblk = gn_cp ? a.gn_nblk : 0;
+  p.reduce = zdim == 1 ? RED_NONE : (gn_apply ? RED_GN_APPLY : (gn_fuse ? RED_GN_PARTIALS : RED_PLAIN));
+}
 
-#ifdef UPK_TIMELINE
-  {  // dev: UPK_TL_TARGET=n stamps only the n-th conv launch of the process (e.g. one launch inside the forward graph)
-    static int launch_no = 0;
-    static const char* tgt = getenv("UPK_TL_TARGET");
-    if (tgt) {
-      a.flags &= ~ABL_TIMELINE;
-      if (launch_no == atoi(tgt)) {
-        a.flags |= ABL_TIMELINE;
-        fprintf(stderr, "[timeline] launch %d: M=%d npad=%d nchunks=%d ks=%d cfg=%s(%d) splitk=%d flags=%x res=%d rowvec=%d\n", launch_no,
-                a.M, a.npad, a.nchunks, a.ks, upk_conv_config_name(best), best, zdim, flags, a.res != nullptr, a.rowvec != nullptr);
-      }
-      ++launch_no;
-    }
-  }
-#endif
-  upk_prof_scope prof(ctx, UPK_CLS_IGEMM, stream);
-  // XCD-aware tile order (tile_map): choose the pm x pn split of the 8 XCDs that minimises the bytes pulled over the
-  // fabric — weights by pm XCDs, activations by pn — against the default order (tile index round-robin), measured at
-  // 3.5-7x the algorithmic bytes on the 16x16 ... 4x4 levels (scripts/pmc_fetch.sh)
+// Plan step 4, the XCD-aware tile order (tile_map), and with it the grid: choose the pm x pn split of the 8 XCDs that
+// minimises the bytes pulled over the fabric — weights by pm XCDs, activations by pn — against the default order (tile
+// index round-robin), measured at 3.5-7x the algorithmic bytes on the 16x16 ... 4x4 levels (scripts/pmc_fetch.sh)
+static void conv_tile_order(const upk_ctx* ctx, ConvPlan& p) {
+  IgemmArgs& a = p.a;
+  const int zdim = p.zdim, nph = p.nph, BM = p.bm;
   a.xm_pm = 0;
   a.xm_z = zdim;
-  dim3 grid(a.tiles_m * a.tiles_n, nph, zdim);
+  p.grid = dim3(a.tiles_m * a.tiles_n, nph, zdim);
   {
     const long units = (long)a.tiles_n * zdim;
     const double Ab = (double)a.B * a.HS * a.WS * (a.c1 + a.c2) * 2.0 + (double)a.M * (a.c3 + a.c4) * 2.0;
@@ -1545,17 +1538,50 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
         a.xm_nj = nj;
       }
     }
-    if (a.xm_pm) grid = dim3(8 * a.xm_mi * a.xm_nj, nph, 1);
+    if (a.xm_pm) p.grid = dim3(8 * a.xm_mi * a.xm_nj, nph, 1);
   }
-  if (is_as) return astat_launch(ctx, a, best - kNumCfgs, aspl, grid, stream);
+}
+
+static int conv_plan(upk_ctx* ctx, const upk_conv_desc* d, int want_cfg, int want_sk, ConvPlan* p) {
+  if (int rc = conv_translate(ctx, d, p->a)) return rc;
+  p->nph = p->a.ph_on ? 4 : 1;
+  if (int rc = conv_pick(ctx, *p, want_cfg, want_sk)) return rc;
+  conv_byproducts(*p, d);
+  conv_tile_order(ctx, *p);
+  return UPK_OK;
+}
+
+// Enqueues the kernel of the plan and its reduce pass.  Decides nothing.
+static int conv_launch(upk_ctx* ctx, const ConvPlan& p, const upk_conv_desc* d, hipStream_t stream) {
+  IgemmArgs a = p.a;  // (a copy: the dev hook below marks single launches)
+  const int zdim = p.zdim;
+#ifdef UPK_TIMELINE
+  {  // dev: UPK_TL_TARGET=n stamps only the n-th conv launch of the process (e.g. one launch inside the forward graph)
+    static int launch_no = 0;
+    static const char* tgt = getenv("UPK_TL_TARGET");
+    if (tgt) {
+      a.flags &= ~ABL_TIMELINE;
+      if (launch_no == atoi(tgt)) {
+        const int cfg = family_base(p.family) + p.cfg;
+        a.flags |= ABL_TIMELINE;
+        fprintf(stderr, "[timeline] launch %d: M=%d npad=%d nchunks=%d ks=%d cfg=%s(%d) splitk=%d flags=%x res=%d rowvec=%d\n", launch_no,
+                a.M, a.npad, a.nchunks, a.ks, upk_conv_config_name(cfg), cfg, zdim, d->flags, a.res != nullptr, a.rowvec != nullptr);
+      }
+      ++launch_no;
+    }
+  }
+#endif
+  upk_prof_scope prof(ctx, UPK_CLS_IGEMM, stream);
+  if (p.family == FAM_ASTAT) return astat_launch(ctx, a, p.cfg, p.as, p.grid, p.block, stream);
   int rc;
-  if (is_bt) rc = bt_launch(ctx, a, best - bt0, grid, stream);
+  if (p.family == FAM_BIGTILE) rc = bt_launch(ctx, a, p.cfg, p.grid, p.block, stream);
   else {
-  hipLaunchKernelGGL((a.ln_u && !a.lnr_in) ? c.fn_ln : (a.x3 ? c.fn_app : c.fn), grid, dim3(c.nbuf ? 512 : c.wm * c.wn * 64), 0, stream, a);
-  rc = upk_check_launch(ctx, "igemm");
+    const CfgInfo& c = kCfgs[p.cfg];
+    hipLaunchKernelGGL((a.ln_u && !a.lnr_in) ? c.fn_ln : (a.x3 ? c.fn_app : c.fn), p.grid, p.block, 0, stream, a);
+    rc = upk_check_launch(ctx, "igemm");
   }
   if (rc) return rc;
-  if (zdim > 1 && gn_apply) {
+  if (p.reduce == RED_GN_APPLY) {
     GnApply g;
     g.gamma = d->gno_gamma;
     g.beta = d->gno_beta;
@@ -1567,12 +1593,12 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
     g.cpg = a.n_out / d->gn_groups;
     g.hw = a.Ho * a.Wo;
     const dim3 gg(d->gn_groups, a.B);
-    if (ga_nv <= 1)
+    if (p.ga_nv <= 1)
       hipLaunchKernelGGL((igemm_reduce_gnapply_kernel<4, 1>), gg, dim3(256), 0, stream, a, zdim, g);
     else
       hipLaunchKernelGGL((igemm_reduce_gnapply_kernel<4, 2>), gg, dim3(256), 0, stream, a, zdim, g);
     rc = upk_check_launch(ctx, "igemm_reduce_gnapply");
-  } else if (zdim > 1 && gn_fuse) {
+  } else if (p.reduce == RED_GN_PARTIALS) {
     GnFuse gf;
     gf.ws = d->gn_stats_ws;
     gf.groups = d->gn_groups;
@@ -1581,28 +1607,45 @@ static int conv_impl(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream_, b
     upk_gn_chunking(gf.hw, &gf.nchunks, &gf.pix_per_chunk);
     hipLaunchKernelGGL(igemm_reduce_gn_kernel, dim3(gf.nchunks, a.B), dim3(256), 0, stream, a, zdim, gf);
     rc = upk_check_launch(ctx, "igemm_reduce_gn");
-  } else if (zdim > 1) {
+  } else if (p.reduce == RED_PLAIN) {
     const long total = (long)a.M * (a.npad / 4);
-    hipLaunchKernelGGL(igemm_reduce_kernel, dim3((unsigned)((total + 255) / 256), nph), dim3(256), 0, stream, a, zdim);
+    hipLaunchKernelGGL(igemm_reduce_kernel, dim3((unsigned)((total + 255) / 256), p.nph), dim3(256), 0, stream, a, zdim);
     rc = upk_check_launch(ctx, "igemm_reduce");
   }
   return rc;
 }
 
+// The plan of a production launch: its request is the context's override if set, else the descriptor's tuned pair
+static int conv_plan_requested(upk_ctx* ctx, const upk_conv_desc* d, ConvPlan* p) {
+  if (!ctx || !d) return UPK_EINVAL;
+  const int want_cfg = ctx->cfg_override >= 0 ? ctx->cfg_override : (d->tune_cfg > 0 ? d->tune_cfg - 1 : -1);
+  const int want_sk = ctx->splitk_override > 0 ? ctx->splitk_override : (d->tune_splitk > 0 ? d->tune_splitk : 0);
+  return conv_plan(ctx, d, want_cfg, want_sk, p);
+}
+
 extern "C" int upk_conv2d_nhwc_f16(upk_ctx* ctx, const upk_conv_desc* d, upk_stream stream) {
-  return conv_impl(ctx, d, stream, true, nullptr);
+  ConvPlan p;
+  if (int rc = conv_plan_requested(ctx, d, &p)) return rc;
+  return conv_launch(ctx, p, d, (hipStream_t)stream);
 }
 
 extern "C" int upk_conv_ln_rows(upk_ctx* ctx, const upk_conv_desc* d, int* slots) {
   if (!slots) return UPK_EINVAL;
-  return conv_impl(ctx, d, nullptr, false, nullptr, nullptr, slots);
+  *slots = 0;
+  ConvPlan p;
+  const int rc = conv_plan_requested(ctx, d, &p);
+  if (rc == UPK_OK) *slots = p.lnr_slots;
+  return rc;
 }
 
 extern "C" int upk_conv_gn_fused(upk_ctx* ctx, const upk_conv_desc* d, int* mode, int* nblk) {
   if (!mode || !nblk) return UPK_EINVAL;
   *mode = 0;
   *nblk = 0;
-  return conv_impl(ctx, d, nullptr, false, mode, nblk);
+  ConvPlan p;
+  const int rc = conv_plan_requested(ctx, d, &p);
+  if (rc == UPK_OK) *mode = p.gn_mode, *nblk = p.gn_nblk;
+  return rc;
 }
 
 constexpr float kGnStatsLaunchUs = 5.0f;  // gn_stats_kernel inside the replayed forward (rocprof: 5.7 us average)
@@ -1627,21 +1670,18 @@ extern "C" int upk_conv_autotune(upk_ctx* ctx, const upk_conv_desc* d, upk_strea
     (void)hipEventDestroy(e0);
     return upk_fail(ctx, UPK_EHIP, "autotune: hipEventCreate failed");
   }
-  const int save_cfg = ctx->cfg_override, save_sk = ctx->splitk_override;
-  upk_conv_desc dd = *d;
-  dd.tune_cfg = 0;
-  dd.tune_splitk = 0;
+  ConvPlan p;  // of the launch timed last
   auto time_one = [&](int cfg, int sk, float* us) -> int {
-    ctx->cfg_override = cfg;
-    ctx->splitk_override = sk;
-    int rc = upk_conv2d_nhwc_f16(ctx, &dd, stream);  // warm-up + feasibility
+    // the candidate is the request: every repetition plans and launches like a production launch
+    auto run = [&] { const int rc = conv_plan(ctx, d, cfg, sk, &p); return rc ? rc : conv_launch(ctx, p, d, stream); };
+    int rc = run();  // warm-up + feasibility
     if (rc) return rc;
     if (cold) {
       float tot = 0.f;
       for (int r = 0; r < reps; ++r) {
         if (hipMemsetAsync(flush_buf, r, flush_bytes, stream) != hipSuccess) return UPK_EHIP;
         if (hipEventRecord(e0, stream) != hipSuccess) return UPK_EHIP;
-        rc |= upk_conv2d_nhwc_f16(ctx, &dd, stream);
+        rc |= run();
         if (hipEventRecord(e1, stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) return UPK_EHIP;
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess) return UPK_EHIP;
@@ -1651,7 +1691,7 @@ extern "C" int upk_conv_autotune(upk_ctx* ctx, const upk_conv_desc* d, upk_strea
       return rc;
     }
     if (hipEventRecord(e0, stream) != hipSuccess) return UPK_EHIP;
-    for (int r = 0; r < reps; ++r) rc |= upk_conv2d_nhwc_f16(ctx, &dd, stream);
+    for (int r = 0; r < reps; ++r) rc |= run();
     if (hipEventRecord(e1, stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) return UPK_EHIP;
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess) return UPK_EHIP;
@@ -1663,14 +1703,12 @@ extern "C" int upk_conv_autotune(upk_ctx* ctx, const upk_conv_desc* d, upk_strea
   float best = 1e30f;
   int bc = -1, bs = 1;
   if (rc == UPK_OK) {
-    const int sks[] = {1, 2, 3, 4, 6, 8, 9, 12, 16, 18};
     for (int c = 0; c < upk_conv_num_configs(); ++c)
-      for (int sk : sks) {
+      for (int sk : kSplitKs) {
         float us = 0.f;
         if (time_one(c, sk, &us) != UPK_OK) continue;  // infeasible candidate
         // a split launch whose reduce pass writes the GroupNorm partials saves the consumer's gn_stats launch
-        int fused = 0;
-        if (dd.gn_stats_ws && conv_impl(ctx, &dd, nullptr, false, &fused) == UPK_OK && fused) us -= kGnStatsLaunchUs;  // either mode
+        if (d->gn_stats_ws && p.gn_mode) us -= kGnStatsLaunchUs;  // any mode
         if (us < best) {
           best = us;
           bc = c;
@@ -1679,8 +1717,6 @@ extern "C" int upk_conv_autotune(upk_ctx* ctx, const upk_conv_desc* d, upk_strea
       }
     ctx->err[0] = 0;
   }
-  ctx->cfg_override = save_cfg;
-  ctx->splitk_override = save_sk;
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   if (rc) return rc;

@@ -124,6 +124,13 @@ __device__ __forceinline__ f32x4 slab_load4(const slab_t* p) {
   return (f32x4){(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
 }
 
+// bytes of one split's slabs, and the rule every family shares for a split-K factor: the slabs fit the workspace, a
+// split has at least 4 chunks, and the folded LayerNorm needs the whole K in one block
+inline size_t slab_bytes(const IgemmArgs& a) { return (size_t)a.M * a.npad * sizeof(slab_t) * (a.ph_on ? 4 : 1); }
+inline bool splitk_fits(const upk_ctx* ctx, const IgemmArgs& a, int sk) {
+  return sk <= 1 || (!a.ln_u && slab_bytes(a) * sk <= ctx->ws_bytes && a.nchunks / sk >= 4);
+}
+
 // (tm, tn, split index) of this workgroup; false: nothing to do (XCD-aware grids are padded)
 __device__ __forceinline__ bool tile_map(const IgemmArgs& a, int& tm, int& tn, int& zs) {
   if (a.xm_pm == 0) {
@@ -634,24 +641,27 @@ struct Epi {
 };
 
 
+// The families beside igemm.hip's own table plan alike: X_plan fills the geometry of configuration c for the launch
+// translated into `a` and the second slot of the tuning pair; false = outside the family's domain.  Neither touches the
+// device; X_launch enqueues on the grid and block the planner (conv_plan, igemm.hip) chose.
 // astat.hip: the A-stationary family (configurations kNumCfgs .. of upk_conv_config_name)
 struct AsPlan {
-  int bm, pw, npass, ppw, tiles_m, tiles_n, lds_bytes;
+  int bm, pw, ni, npass, ppw, tiles_m, tiles_n, lds_bytes;
 };
 int astat_num_configs();
 const char* astat_config_name(int c);
-int astat_config_ni(int c);
 bool astat_plan(const upk_ctx* ctx, const IgemmArgs& a, int c, int ppw_req, AsPlan* pl);
-int astat_launch(upk_ctx* ctx, IgemmArgs& a, int c, const AsPlan& pl, dim3 grid, hipStream_t stream);
+int astat_launch(upk_ctx* ctx, const IgemmArgs& a, int c, const AsPlan& pl, dim3 grid, dim3 block, hipStream_t stream);
 
 // bigtile.hip: the big-tile family (configurations behind the A-stationary ones): 4 waves, one per SIMD, 256x256 /
 // 256x128 / 128x256 block tiles for launches with at least one tile per CU
+struct BtPlan {
+  int bm, bn, occ, mi, ni, wn, threads;  // block tile, workgroups per CU, fragments per wave, N waves, block size
+};
 int bt_num_configs();
 const char* bt_config_name(int c);
-void bt_tile(int c, int* bm, int* bn, int* occ, int* mi, int* ni, int* wn);
-bool bt_full_epilogue(int c);  // the configuration also exists with the general epilogue (Epi::tile)
-int bt_launch(upk_ctx* ctx, const IgemmArgs& a, int c, dim3 grid, hipStream_t stream);
-
+bool bt_plan(const upk_ctx* ctx, const IgemmArgs& a, int c, int splitk, BtPlan* pl);
+int bt_launch(upk_ctx* ctx, const IgemmArgs& a, int c, dim3 grid, dim3 block, hipStream_t stream);
 
 
 }  // namespace upkd
