@@ -618,8 +618,32 @@ int upk_plms_step_f32(upk_ctx* ctx, float* x, const float* eps, const float* coe
 int upk_dpmpp_2m_step_f32(upk_ctx* ctx, float* x, const float* eps, const float* coefs, const int32_t* step,
                           float* x0_old, float* pred_x0, void* xin, int ld_xin, int batch, int c, int hw,
                           int first_row, float cfg_scale, int cfg, upk_stream stream);
+/* One model evaluation of UniPC (Zhao et al. 2023, arXiv:2302.04867: multistep predictor-corrector on the data prediction,
+ * orders 1 - 3, eta = 0), fp32 NCHW, n = B*C*H*W elements.  Points are numbered k = 0 .. S along the chain (lambda =
+ * log(alpha / sigma) ascends); evaluation k = *step sees the predicted latent x at point k, forms m_k, corrects the step
+ * k-1 -> k with it and predicts the step k -> k+1 from the corrected latent.  row = coefs + 12 * (*step), h_c = lambda_k -
+ * lambda_{k-1}, h_p = lambda_{k+1} - lambda_k (upgpt_amd/schedule.py unipc_coefficient_table):
+ *   {sigma_k, 1/alpha_k,
+ *    sigma_k/sigma_{k-1}, -alpha_k expm1(-h_c), weights of (m_k - m_{k-1}), (m_{k-2} - m_{k-1}), (m_{k-3} - m_{k-1}),
+ *    sigma_{k+1}/sigma_k, -alpha_{k+1} expm1(-h_p), weights of (m_{k-1} - m_k), (m_{k-2} - m_k),
+ *    1 if the corrector runs else 0}
+ *   e  = eps, or with cfg != 0 e_u + cfg_scale * (e_c - e_u) from eps = [uncond ; cond] (2*batch rows)
+ *   m  = (x - row[0]*e) * row[1]
+ *   xc = row[11] != 0 ? row[2]*x_corr + row[3]*h0 + row[4]*(m - h0) [+ row[5]*(h1 - h0)] [+ row[6]*(h2 - h0)] : x
+ *   xn = row[7]*xc + row[8]*m [+ row[9]*(h0 - m)] [+ row[10]*(h1 - m)]
+ *   x_corr = xc;  x = xn;  pred_x0 = m (may be NULL)
+ * hist: fp32 [3, n] ring owned by the caller; h0, h1, h2 = m of evaluations *step - 1, - 2, - 3 in slots (*step - j) mod 3,
+ * and m goes to slot *step mod 3 (h2's, read before it is written).  x_corr: fp32 [n], the last corrected latent.  A
+ * bracketed term runs only where its weight is non-zero, and neither it nor a corrector with row[11] = 0 loads its
+ * operands: hist and x_corr need no initialisation, the rows of a chain say what exists.  step == NULL: row 0.
+ * Refreshes the UNet stem input xin like upk_ddim_step_f32 (with cfg both halves, 2*batch*hw rows); x is updated in
+ * place; honours upk_step_autoadvance.  UPK_EINVAL for a missing operand, a non-positive extent, ld_xin < c with xin,
+ * or a pointer that is not aligned to its element. */
+int upk_unipc_step_f32(upk_ctx* ctx, float* x, const float* eps, const float* coefs, const int32_t* step, float* hist,
+                       float* x_corr, float* pred_x0, void* xin, int ld_xin, int batch, int c, int hw, float cfg_scale,
+                       int cfg, upk_stream stream);
 /* With done != NULL the sampler step kernels launched afterwards (upk_ddim_step_f32, upk_ddim_step_cfg_f32,
- * upk_ddim_step_edit_f32, upk_plms_step_f32, upk_ddpm_step_f32, upk_dpmpp_2m_step_f32) add 1 to *step THEMSELVES once every workgroup has read it (done: a zero-initialised device
+ * upk_ddim_step_edit_f32, upk_plms_step_f32, upk_ddpm_step_f32, upk_dpmpp_2m_step_f32, upk_unipc_step_f32) add 1 to *step THEMSELVES once every workgroup has read it (done: a zero-initialised device
  * int32 they use as arrival counter and leave at zero) — one launch less per sampler step than upk_advance_step.
  * done == NULL restores the plain behaviour.  Host-side state of the context: set it around the calls. */
 int upk_step_autoadvance(upk_ctx* ctx, int32_t* done);

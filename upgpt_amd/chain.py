@@ -1,4 +1,5 @@
-"""The captured-chain driver the four samplers share (DDIM with its editing chains, PLMS, DDPM ancestral, DPM-Solver++(2M)):
+"""The captured-chain driver the five samplers share (DDIM with its editing chains, PLMS, DDPM ancestral, DPM-Solver++(2M),
+UniPC):
 how a chain's steps are grouped into graph launches, the loop that launches the groups and hands control back to the
 sampler between them, the start latent, and the lock rule in front of the loop.  What stays with each
 sampler is what a caller can observe: its tables and draws in front of the loop, and its host work after a group
@@ -64,6 +65,7 @@ def upload_lock(take):
       DDIM  fresh or on_host or (with_noise and not keyed)   # unkeyed step noise: S draws and row copies
       PLMS  fresh or on_host                                 # eta = 0: its discarded draws touch no table
       DPM   fresh or on_host or (x_T is None and not keyed)  # the only draw is x_T
+      UniPC as DPM
       DDPM  always                                           # uploads its coefficient and temperature rows every call
 
     fresh: a timestep-row, coefficient or noise-scale table of this call differs from what the device holds."""

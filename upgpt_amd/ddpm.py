@@ -641,10 +641,12 @@ class LatentDiffusion(AncestralSampling, DDPM):
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, sampler="ddim", **kwargs):
         """ddpm.py:1312-1325.  sampler (this package's extension; it arrives through log_images' **kwargs, so test_step,
-        evaluate.run_test / run_upscale and InferenceModel.generate take it too): "ddim", or "dpmpp_2m" for
-        DPM-Solver++(2M) on its logSNR grid (dpm_solver.py) — ddim_steps is then its step count, and `eta`, DDIM's knob
-        (log_images passes its ddim_eta default of 1), does not apply to the deterministic solver and is dropped."""
-        require(sampler in ("ddim", "dpmpp_2m"), lambda: "sampler %r (ddim or dpmpp_2m)" % (sampler,), ValueError)
+        evaluate.run_test / run_upscale and InferenceModel.generate take it too): "ddim", "dpmpp_2m" for
+        DPM-Solver++(2M) on its logSNR grid (dpm_solver.py) or "unipc" for UniPC on the same grid (unipc.py; its order /
+        variant / corrector arguments pass through **kwargs, and it refuses a masked chain) — ddim_steps is then the step
+        count, and `eta`, DDIM's knob (log_images passes its ddim_eta default of 1), does not apply to the deterministic
+        solvers and is dropped."""
+        require(sampler in ("ddim", "dpmpp_2m", "unipc"), lambda: "sampler %r (ddim, dpmpp_2m or unipc)" % (sampler,), ValueError)
         if not ddim:
             return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, **kwargs)
         shape = (self.channels, *self.image_size)
@@ -652,6 +654,10 @@ class LatentDiffusion(AncestralSampling, DDPM):
             from .dpm_solver import DPMSolverSampler
             kwargs.pop("eta", None)
             return DPMSolverSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
+        if sampler == "unipc":
+            from .unipc import UniPCSampler
+            kwargs.pop("eta", None)
+            return UniPCSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
         return DDIMSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
 
     def _get_denoise_row_from_list(self, samples, desc="", force_no_decoder_quantization=False):

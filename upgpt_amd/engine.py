@@ -634,6 +634,9 @@ class SamplerState:
               mask: at B = 8, 32x24 and 1000 steps each table is 1000 * 24576 * 4 B = 98 MB.
       "dpm":  one DPM-Solver++(2M) step, upk_dpmpp_2m_step_f32 (coefficient rows of 8); x0_old [n] is the data prediction of
               the step before, which the kernel reads on second-order rows only, so nothing initialises it.
+      "unipc": one UniPC model evaluation, upk_unipc_step_f32 (coefficient rows of 12): the corrector of the step that led to
+              this point and the predictor of the next.  hist [3, n] is the ring of data predictions and x_corr [n] the last
+              corrected latent; the rows say which of them exist, so nothing initialises them either.
     cfg: classifier-free guidance — the plan runs 2*B rows ([unconditional ; conditional], ddim.py:173-178), the latent
     state has B = plan.B // 2 samples and the update combines the two halves of eps."""
 
@@ -652,11 +655,12 @@ class SamplerState:
         self.C = channels
         self.x = plan.alloc(B, channels, H, W, dtype=torch.float32)
         self.pred_x0 = plan.alloc(B, channels, H, W, dtype=torch.float32)
-        self.coefs = plan.alloc(R, 8 if kind in ("ddpm", "dpm") else 4, dtype=torch.float32)
+        self.coefs = plan.alloc(R, {"ddpm": 8, "dpm": 8, "unipc": 12}.get(kind, 4), dtype=torch.float32)
         self.noise = None
         self.graphs = {}  # (with_noise, scale, nsteps, variant) -> instantiated graph, least recently used first
         self.step_done = plan.alloc(1, dtype=torch.int32, zero=True)  # arrival counter of the step kernels
-        self.hist = plan.alloc(3, B * channels * H * W, dtype=torch.float32) if kind == "plms" else None
+        self.hist = plan.alloc(3, B * channels * H * W, dtype=torch.float32) if kind in ("plms", "unipc") else None
+        self.x_corr = plan.alloc(B * channels * H * W, dtype=torch.float32) if kind == "unipc" else None
         self.x0_old = plan.alloc(B * channels * H * W, dtype=torch.float32) if kind == "dpm" else None
         self.set_variant((0, False) if kind == "ddpm" else None)
 
@@ -742,7 +746,15 @@ class SamplerState:
             self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(), p.step.data_ptr(), self.x0_old.data_ptr(),
             self.pred_x0.data_ptr(), p.xin.t.data_ptr(), p.xin.ld, self.B, self.C, p.H * p.W, 0, float(scale), int(self.cfg))
 
-    _STEP = {"ddim": _ddim_step, "plms": _plms_step, "ddpm": _ddpm_step, "dpm": _dpm_step}
+    def _unipc_step(self, nz, scale):
+        p = self.plan
+        require(nz is None, "UniPC runs with eta = 0", ValueError)
+        return p.lib.upk_unipc_step_f32, (
+            self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(), p.step.data_ptr(), self.hist.data_ptr(),
+            self.x_corr.data_ptr(), self.pred_x0.data_ptr(), p.xin.t.data_ptr(), p.xin.ld, self.B, self.C, p.H * p.W,
+            float(scale), int(self.cfg))
+
+    _STEP = {"ddim": _ddim_step, "plms": _plms_step, "ddpm": _ddpm_step, "dpm": _dpm_step, "unipc": _unipc_step}
 
     def _ensure(self, with_noise):
         """The buffers the step of (kind, variant) reads besides the state's own."""

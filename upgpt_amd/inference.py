@@ -184,8 +184,8 @@ class InferenceModel:
 
     def generate(self, batch, steps=200, repeat=1, use_ema=True, sampler="ddim", noise_keys=None):
         """log_images with the demo's settings -> {'reconstruction'?, 'samples'} as float numpy [b, h, w, 3] in [0, 1]
-        (:160-170; `repeat` is unused there as well).  sampler: "ddim" (the reference's), or "dpmpp_2m" for
-        DPM-Solver++(2M) with `steps` steps (LatentDiffusion.sample_log).  noise_keys (upgpt_amd.rng.NoiseKeys, one key
+        (:160-170; `repeat` is unused there as well).  sampler: "ddim" (the reference's), "dpmpp_2m" for
+        DPM-Solver++(2M) or "unipc" for UniPC, each with `steps` steps (LatentDiffusion.sample_log).  noise_keys (upgpt_amd.rng.NoiseKeys, one key
         per sample): handed to log_images, which then draws keyed noise instead of the torch generator's."""
         extra = {} if sampler == "ddim" else {"sampler": sampler}
         if noise_keys is not None:
@@ -313,6 +313,9 @@ class InferenceModel:
                 v = np.asarray(v.convert(mode) if mode == "RGB" else v, dtype=np.uint8)
             return v
         edit.region_labels(region, segmenter)  # (everything refusable is refused before anything is uploaded)
+        if sampler == "unipc":  # (a region edit is a masked chain)
+            from .unipc import _MASKED
+            raise NotImplementedError(_MASKED)
         require(0 <= int(dilate) <= edit.MAX_DILATE, lambda: "dilate must be 0 .. %d, got %r" % (edit.MAX_DILATE, dilate), ValueError)
         require(0 <= int(feather) <= edit.MAX_FEATHER, lambda: "feather must be 0 .. %d, got %r" % (edit.MAX_FEATHER, feather),
                 ValueError)

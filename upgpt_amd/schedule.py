@@ -6,7 +6,7 @@ DDIM selection and sigmas per util.py:46-74.  The per-step scalars that the refe
 re-materialises with torch.full every step (ddim.py:189-192) are folded here into ONE
 device table of 4 fp32 coefficients per step for upk_ddim_step_f32 (8 per step for the DDPM
 step, upk_ddpm_step_f32, and for the DPM-Solver++(2M)
-step, upk_dpmpp_2m_step_f32).
+step, upk_dpmpp_2m_step_f32; 12 for the UniPC step, upk_unipc_step_f32).
 """
 import numpy as np
 import torch
@@ -106,6 +106,70 @@ def dpm_coefficient_table(alphas, alphas_prev, order=2, lower_order_final=None):
             w[-1] = 0.0
     rows = np.zeros((S, 8))
     rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3], rows[:, 4] = sg_t, 1.0 / al_t, sg_p / sg_t, -al_p * np.expm1(-h), w
+    return torch.from_numpy(rows.astype(np.float32)).contiguous()
+
+
+def _unipc_rho(r, h, variant):
+    """The solution rho of UniPC's system R rho = b (Zhao et al. 2023, theorem 3.1) for the nodes r = [r_1 .. r_n]:
+    R[i][j] = r_j^i, b[i] = (i + 1)! z phi_{i+2}(z) / B(h) with z = -h (the data prediction's sign), phi_1(z) = expm1(z) / z,
+    phi_{k+1}(z) = (phi_k(z) - 1 / k!) / z, i = 0 .. n - 1; fp64."""
+    n, hh = len(r), -h
+    B = np.expm1(hh) if variant == "bh2" else hh
+    phi, fact, b = np.expm1(hh) / hh - 1.0, 1.0, []
+    for i in range(1, n + 1):
+        b.append(phi * fact / B)
+        fact *= i + 1
+        phi = phi / hh - 1.0 / fact
+    R = np.asarray([[rj ** i for rj in r] for i in range(n)], dtype=np.float64)
+    return np.linalg.solve(R, np.asarray(b, dtype=np.float64))
+
+
+def unipc_coefficient_table(alphas, alphas_prev, order=2, variant="bh2", lower_order_final=True, corrector=True, start=0):
+    """[S - start, 12] fp32 rows of upk_unipc_step_f32 in LOOP order from the DDIM tables `alphas` / `alphas_prev` (ascending
+    index).  The chain's points are numbered k = 0 .. S in loop order (point k < S is DDIM index S - 1 - k, point S the last
+    target alphas_prev[0]), lambda = log(alpha / sigma) ascends; the chain starts at point `start` with no history.  Row
+    k - start belongs to the model evaluation at point k (include/upk.h for the layout):
+      predictor k -> k+1 of order p_k = min(order, k + 1 - start, S - k) (the last term with lower_order_final), on the nodes
+        r_i = (lambda_{k-i} - lambda_k) / h_p, i = 1 .. p_k - 1: weights -alpha_{k+1} B(h_p) rho_i / r_i, rho from the system
+        without its last row and column, [0.5] at order 2;
+      corrector of k-1 -> k (none at point `start`, none with corrector=False) of order p_{k-1}, nodes r_i = (lambda_{k-1-i} -
+        lambda_{k-1}) / h_c and r = 1 for m_k itself: weights -alpha_k B(h_c) rho_i / r_i, [0.5] at order 1.
+    B(h) = expm1(-h) ("bh2") or -h ("bh1").  Computed in fp64 and rounded once."""
+    if order not in (1, 2, 3):
+        raise ValueError("unipc_coefficient_table: order %r (1, 2 or 3)" % (order,))
+    if variant not in ("bh1", "bh2"):
+        raise ValueError("unipc_coefficient_table: variant %r (bh1 or bh2)" % (variant,))
+    f64 = lambda v: np.asarray(torch.as_tensor(v).detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float64)
+    a_t, a_p = f64(alphas)[::-1], f64(alphas_prev)[::-1]
+    S, start = int(a_t.shape[0]), int(start)
+    if not 0 <= start < S:
+        raise ValueError("unipc_coefficient_table: start %d outside the %d-step chain" % (start, S))
+    a = np.concatenate([a_t, a_p[-1:]])  # the S + 1 points
+    al, sg = np.sqrt(a), np.sqrt(1.0 - a)
+    lam = np.log(al / sg)
+    if not (np.diff(lam) > 0).all():
+        raise ValueError("unipc_coefficient_table: the logSNR must rise along the chain")
+    B = (lambda h: np.expm1(-h)) if variant == "bh2" else (lambda h: -h)
+    p_of = lambda k: min(order, k + 1 - start, S - k if lower_order_final else order)
+    rows = np.zeros((S - start, 12))
+    for k in range(start, S):
+        row, p = rows[k - start], p_of(k)
+        row[0], row[1] = sg[k], 1.0 / al[k]
+        h = lam[k + 1] - lam[k]
+        row[7], row[8] = sg[k + 1] / sg[k], -al[k + 1] * np.expm1(-h)
+        if p > 1:
+            r = [(lam[k - i] - lam[k]) / h for i in range(1, p)]
+            rho = np.asarray([0.5]) if p == 2 else _unipc_rho(r, h, variant)
+            row[9:9 + p - 1] = -al[k + 1] * B(h) * rho / np.asarray(r)
+        if corrector and k > start:
+            q = p_of(k - 1)
+            h = lam[k] - lam[k - 1]
+            r = [(lam[k - 1 - i] - lam[k - 1]) / h for i in range(1, q)] + [1.0]
+            rho = np.asarray([0.5]) if q == 1 else _unipc_rho(r, h, variant)
+            row[2], row[3] = sg[k] / sg[k - 1], -al[k] * np.expm1(-h)
+            row[4] = -al[k] * B(h) * rho[-1]
+            row[5:5 + q - 1] = -al[k] * B(h) * rho[:-1] / np.asarray(r[:-1])
+            row[11] = 1.0
     return torch.from_numpy(rows.astype(np.float32)).contiguous()
 
 
