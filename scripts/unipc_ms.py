@@ -1,4 +1,4 @@
-"""Call time of DPM-Solver++(2M) at 20 steps against UniPC at the step counts under discussion (12, 15, 20; DESIGN.md 40)
+"""Call time of DPM-Solver++(2M) at 20 steps against UniPC at the step counts under discussion (12, 15, 20; DESIGN.md 41)
 on the MI355X, at the benchmark's shape: bbox model, bs 8, 32x32 latent, sample() on the captured-graph fast path +
 decode_first_stage, from entry to a device synchronise.  All run in ONE process and alternate within each of --rounds
 rounds after a warm-up of all (plans, graphs, tables); median, min and max of the call time, the pictures per second at the

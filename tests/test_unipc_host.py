@@ -145,7 +145,7 @@ def test_predictor_of_order_two_is_dpmpp_2m(s2):
     assert abs(R.gaussian_error(ACP64, s2, S, 2, corrector=False) - D.gaussian_error(ACP64, s2, "2m", "logsnr", S)) < 1e-9
 
 
-# what the fp64 experiment behind DESIGN.md 40 gave, two digits: rows (order, S), columns s^2 = 0.25, 1, 4
+# what the fp64 experiment behind DESIGN.md 41 gave, two digits: rows (order, S), columns s^2 = 0.25, 1, 4
 TABLE = {(2, 12): (8.2e-3, 9.6e-3, 9.8e-3), (2, 20): (2.1e-3, 2.3e-3, 2.3e-3), (2, 25): (8.7e-4, 1.1e-3, 1.2e-3),
          (2, 50): (1.4e-4, 8.2e-5, 1.4e-4), (3, 12): (3.9e-3, 1.1e-3, 6.6e-4), (3, 15): (6.6e-4, 2.6e-4, 9.4e-5)}
 

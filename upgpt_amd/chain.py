@@ -1,9 +1,10 @@
 """The captured-chain driver the five samplers share (DDIM with its editing chains, PLMS, DDPM ancestral, DPM-Solver++(2M),
 UniPC):
 how a chain's steps are grouped into graph launches, the loop that launches the groups and hands control back to the
-sampler between them, the start latent, and the lock rule in front of the loop.  What stays with each
-sampler is what a caller can observe: its tables and draws in front of the loop, and its host work after a group
-(callback order and arguments, what it logs).
+sampler between them, the start latent, and the lock rule in front of the loop.  The four samplers of the
+DDIM family observe a chain the same way, so their host work after a group is here too (run_observed); DDPM's differs
+(it logs first and hands the callbacks the timestep and x) and stays in ancestral.py.  What stays with each sampler: its
+tables and draws in front of the loop and the lock rule they need.
 """
 import contextlib
 
@@ -41,6 +42,30 @@ def run(st, total, steps_per_graph, watched, logged, with_noise, scale=1.0, firs
         st.launch(with_noise, scale, n)
         i += n
         yield i - 1
+
+
+def run_observed(st, first_latent, T, steps_per_graph, callback, img_callback, log_every_t, with_noise, scale=1.0,
+                 first=0, plain=False):
+    """run() with the host work the DDIM family shares (DDIM, PLMS, DPM-Solver++, UniPC) after each group that ends at loop
+    position i >= 0: callback(i), img_callback(pred_x0, i), then x and pred_x0 logged where logged_at(T, log_every_t)
+    says so.  Returns the intermediates, which start from `first_latent`.  plain: log st.x_plain (a masked DDIM chain:
+    st.x already holds the blend for the next step, the reference logs the unblended value).  first=-1 with
+    steps_per_graph=1 is PLMS: T + 1 single launches, nothing for the host at its predictor evaluation."""
+    intermediates = {"x_inter": [first_latent], "pred_x0": [first_latent.clone()]}
+    # (steps whose result the host looks at — callbacks, logged intermediates: ddim.py:139-147 — end a graph)
+    watched = callback is not None or img_callback is not None
+    logged = logged_at(T, log_every_t)
+    for i in run(st, T - first, steps_per_graph, watched, logged, with_noise, scale, first):
+        if i < 0:
+            continue
+        if callback:
+            callback(i)
+        if img_callback:
+            img_callback(st.pred_x0.clone(), i)
+        if logged(i):
+            intermediates["x_inter"].append((st.x_plain if plain else st.x).clone())
+            intermediates["pred_x0"].append(st.pred_x0.clone())
+    return intermediates
 
 
 def start_latent(x_T, noise_keys, shape, device, dtype=None):

@@ -184,3 +184,14 @@ __device__ __forceinline__ void step_advance(const int* step, int* done) {
     }
   }
 }
+
+// The fp16 NHWC stem-input row of a 4-channel latent pixel as ONE 8-byte store; element by element when the row is not
+// 8-byte aligned (a plan's ld_xin need not be a multiple of 4 halves).
+__device__ __forceinline__ void upk_stem_row_store4(f16* row, f16x4 v) {
+  if ((((uintptr_t)row) & 7) == 0) {
+    *(f16x4*)row = v;
+  } else {
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch) row[ch] = v[ch];
+  }
+}

@@ -48,20 +48,8 @@ __global__ void dpmpp_2m_step_kernel(float* x, const float* eps, const float* co
     }
     if (CT == 4 && row) {
       const f16x4 v = {h[0], h[1], h[2], h[3]};
-      if ((((uintptr_t)row) & 7) == 0) {
-        *(f16x4*)row = v;
-      } else {
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch) row[ch] = v[ch];
-      }
-      if (row2) {
-        if ((((uintptr_t)row2) & 7) == 0) {
-          *(f16x4*)row2 = v;
-        } else {
-#pragma unroll
-          for (int ch = 0; ch < 4; ++ch) row2[ch] = v[ch];
-        }
-      }
+      upk_stem_row_store4(row, v);
+      if (row2) upk_stem_row_store4(row2, v);
     }
   }
   if (step) step_advance(step, done);

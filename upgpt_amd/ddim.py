@@ -14,8 +14,11 @@ The editing calls run on the same captured loop (upk_ddim_step_edit_f32): sample
 start at a later row of the same S-row tables.
 
 The loop itself — grouping of steps into graph launches, the start latent, the lock rule of the part in front of it —
-is chain.py's, shared with PLMS, DDPM and DPM-Solver++; this class also holds what its subclasses share with it: the
-schedule cache (_ensure_schedule), the shortened schedule (_subset) and the guided model evaluation (_guided_eps).
+is chain.py's, shared with PLMS, DDPM, DPM-Solver++ and UniPC, and so is the host work after a group of steps
+(chain.run_observed; DDPM keeps its own).  This class also holds what its subclasses share with it: the schedule cache
+(_ensure_schedule), the shortened schedule (_subset), the guided model evaluation (_guided_eps) and the opening of a fast
+path (_open_fast).  The upload-once keys are state of their owners: engine.SamplerState (coefs_fresh / load_coefs,
+scale_fresh / load_noise_scale) and engine.UNetPlan (rows_fresh / load_sampler_inputs).
 """
 import os
 
@@ -168,6 +171,22 @@ class DDIMSampler(object):
         n = len(timesteps)
         return 0 < n <= len(self.ddim_timesteps) and np.array_equal(timesteps, self.ddim_timesteps[:n])
 
+    def _open_fast(self, kind, cond, shape, cfg_scale, uc, rows=None):
+        """How every fast path of this class and its subclasses opens: the conditioning split (with guidance [unconditional ;
+        conditional] for one UNet pass, ddim.py:173-178, combined in the step kernel), the sampler plan of `rows` timestep
+        rows (the schedule's steps; PLMS: its evaluations) and the plan's `kind` state.
+        -> plan, state, c_concat, c_cross, guided."""
+        b, C, H, W = shape
+        cfg = uc is not None and cfg_scale != 1.
+        if cfg:
+            cond = self._cat_cond(uc, cond)
+        c_concat, c_cross = self.model._split_cond(cond)
+        rows = int(self.ddim_timesteps.shape[0]) if rows is None else rows
+        plan = self.model.model.diffusion_model.plan(2 * b if cfg else b, H, W, c_cross.shape[1], rows, "sampler")
+        with torch.cuda.device(plan.dev):
+            st = plan.sampler_state(kind, C, cfg)
+        return plan, st, c_concat, c_cross, cfg
+
     def _fast_sampling(self, cond, shape, x_T, timesteps, callback, img_callback, log_every_t, temperature,
                        normals_sequence, cfg_scale=1., uc=None, mask=None, x0=None, edit=False, noise_keys=None):
         """`timesteps`: the schedule, or a prefix of it (decode, ddim_sampling(timesteps=)): T = len(timesteps) steps
@@ -184,21 +203,14 @@ class DDIMSampler(object):
         masked = mask is not None
         keyed = noise_keys is not None
         require(not masked or x0 is not None, "mask given without x0", ValueError)
-        model = self.model
-        unet = model.model.diffusion_model
-        b, C, H, W = shape
-        cfg = uc is not None and cfg_scale != 1.
-        if cfg:  # one UNet pass over [unconditional ; conditional] (ddim.py:173-178), combined in the update kernel
-            cond = self._cat_cond(uc, cond)
-        c_concat, c_cross = model._split_cond(cond)
+        model, b = self.model, shape[0]
+        plan, st, c_concat, c_cross, cfg = self._open_fast("ddim", cond, shape, cfg_scale, uc)
         S = int(self.ddim_timesteps.shape[0])  # rows of the tables
         T = int(timesteps.shape[0])            # steps of this chain ...
         k = S - T                              # ... which starts at this row
         timesteps = self.ddim_timesteps
-        plan = unet.plan(2 * b if cfg else b, H, W, c_cross.shape[1], S, "sampler")
         dev = plan.dev
         with torch.cuda.device(dev):
-            st = plan.sampler_state("ddim", C, cfg)
             order = np.arange(S)[::-1].copy()  # loop order: descending DDIM index
             sig = torch.as_tensor(np.asarray(self.ddim_sigmas, dtype=np.float64)).float()[torch.as_tensor(order)]
             with_noise = bool((sig[k:] != 0).any())
@@ -208,12 +220,11 @@ class DDIMSampler(object):
             # sampler states of that plan), so their key does too; the coefficient table is this state's own
             rkey = ("ddim", np.asarray(timesteps)[order].astype(np.float32).tobytes())
             ckey = (f64b(self.ddim_alphas), f64b(self.ddim_alphas_prev), f64b(self.ddim_sigmas))
-            fresh_rows = getattr(plan, "_t_rows_key", None) != rkey
-            fresh_coefs = getattr(st, "_coef_key", None) != ckey
+            fresh_coefs = st.coefs_fresh(ckey)
             # (keyed: the per-row scale sigma_i * temperature lives on the device next to the coefficients)
             skey = (ckey, float(temperature))
-            fresh_scale = keyed and with_noise and getattr(st, "_nscale_key", None) != skey
-            fresh = fresh_rows or fresh_coefs or fresh_scale
+            fresh_scale = keyed and with_noise and st.scale_fresh(skey)
+            fresh = plan.rows_fresh(rkey) or fresh_coefs or fresh_scale
             on_host = chain.on_host(x_T, c_concat, c_cross, mask, x0)
             with chain.upload_lock(fresh or on_host or (with_noise and not keyed)):
                 st.x.copy_(chain.start_latent(x_T, noise_keys, shape, dev, torch.float32))
@@ -224,9 +235,8 @@ class DDIMSampler(object):
                     emask.copy_(mask.expand(shape).reshape(-1))
                     desc = np.asarray(timesteps)[order]
                 if fresh_coefs:
-                    st.coefs.copy_(ddim_coefficient_table(self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sigmas,
-                                                          self.ddim_sqrt_one_minus_alphas, order))
-                    st._coef_key = ckey
+                    st.load_coefs(ckey, ddim_coefficient_table(self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sigmas,
+                                                               self.ddim_sqrt_one_minus_alphas, order))
                 # RNG consumption follows the reference: p_sample_ddim draws noise_like(x.shape) in EVERY step, also when
                 # sigma_t == 0 (ddim.py:200, util.py:264-267), so after sample() the device generator has advanced by S
                 # draws of the latent's shape — a caller that seeds once and samples several batches (inference.ipynb)
@@ -238,8 +248,7 @@ class DDIMSampler(object):
                     nz[k:].copy_(ns.to(dev, torch.float32).reshape(T, -1))
                 if keyed:
                     if fresh_scale:
-                        st._nscale = (sig * float(temperature)).to(dev)  # indexed by the absolute row
-                        st._nscale_key = skey
+                        st.load_noise_scale(skey, sig * float(temperature))  # indexed by the absolute row
                     if with_noise:
                         rng.randn(noise_keys, shape, rng.STREAM_STEP, row0=k, rows=T, scale=st._nscale, out=nz[k:])
                     if masked:  # the q_sample noise of every keep row in one launch, then q_sample row by row in place
@@ -259,24 +268,13 @@ class DDIMSampler(object):
                 first = st.x.clone()  # (the reference's intermediates start with the unblended x_T)
                 if masked:  # the blend in front of the first step; the step kernel does the later ones
                     st.x.copy_(keep[k].view(shape) * mask + (1. - mask) * st.x)
-                plan.load_sampler_inputs(torch.cat([st.x, st.x]) if cfg else st.x, c_concat, c_cross, unet.in_channels,
-                                         rkey, np.asarray(timesteps)[order].astype(np.float32))
+                plan.load_sampler_inputs(torch.cat([st.x, st.x]) if cfg else st.x, c_concat, c_cross,
+                                         plan.arch.in_channels, rkey, np.asarray(timesteps)[order].astype(np.float32))
                 plan.step.fill_(k)
                 plan.prep.run()
-            intermediates = {"x_inter": [first], "pred_x0": [first.clone()]}
             print(f"Running DDIM Sampling with {T} timesteps")
-            # (steps whose result the host looks at — callbacks, logged intermediates: ddim.py:139-147 — end a graph)
-            watched = callback is not None or img_callback is not None
-            logged = chain.logged_at(T, log_every_t)
-            for i in chain.run(st, T, STEPS_PER_GRAPH, watched, logged, with_noise, cfg_scale):
-                if callback:
-                    callback(i)
-                if img_callback:
-                    img_callback(st.pred_x0.clone(), i)
-                if logged(i):
-                    # (masked: st.x already holds the blend for the next step; the reference logs the unblended value)
-                    intermediates["x_inter"].append((st.x_plain if masked else st.x).clone())
-                    intermediates["pred_x0"].append(st.pred_x0.clone())
+            intermediates = chain.run_observed(st, first, T, STEPS_PER_GRAPH, callback, img_callback, log_every_t,
+                                               with_noise, cfg_scale, plain=masked)
             return st.x.clone(), intermediates  # (the last step's result is never blended)
 
     # ------------------------------------------------------------------ reference surface

@@ -59,6 +59,7 @@ class UNetPlan(Emitter):
         self.rowvecs = {}
         self.kv = {}
         self.sampler_states = {}  # (kind, guided) -> SamplerState (sampler_state())
+        self._t_rows_key = None   # what t_rows holds (load_sampler_inputs); None: not a sampler's rows
         self.prep = Program(ctx)
         self.body = Program(ctx)
         self._emit_prep()
@@ -248,6 +249,10 @@ class UNetPlan(Emitter):
         while self.sampler_states:
             self.sampler_states.popitem()[1].close()
 
+    def rows_fresh(self, rows_key):
+        """Whether load_sampler_inputs would upload the timestep rows of `rows_key` (a sampler's lock rule asks first)."""
+        return self._t_rows_key != rows_key
+
     def load_sampler_inputs(self, x, c_concat, c_cross, in_channels, rows_key, t_rows):
         """The per-call uploads of a sampler fast path: the latent (channels [0, C) of the stem input), the concat
         conditioning behind it, the context, and the timestep rows when `rows_key` differs from what the plan holds
@@ -261,7 +266,7 @@ class UNetPlan(Emitter):
         require(C + ncat == in_channels, lambda: "latent %d + concat %d != UNet in_channels %d" % (C, ncat, in_channels),
                 ValueError)
         self.load_context(c_cross)
-        if getattr(self, "_t_rows_key", None) != rows_key:
+        if self.rows_fresh(rows_key):
             self.t_rows.copy_(torch.as_tensor(t_rows))
             self._t_rows_key = rows_key
 
@@ -657,6 +662,8 @@ class SamplerState:
         self.pred_x0 = plan.alloc(B, channels, H, W, dtype=torch.float32)
         self.coefs = plan.alloc(R, {"ddpm": 8, "dpm": 8, "unipc": 12}.get(kind, 4), dtype=torch.float32)
         self.noise = None
+        self._coef_key = None  # what `coefs` holds (load_coefs)
+        self._nscale_key = self._nscale = None  # keyed DDIM's per-row noise scale on the device (load_noise_scale)
         self.graphs = {}  # (with_noise, scale, nsteps, variant) -> instantiated graph, least recently used first
         self.step_done = plan.alloc(1, dtype=torch.int32, zero=True)  # arrival counter of the step kernels
         self.hist = plan.alloc(3, B * channels * H * W, dtype=torch.float32) if kind in ("plms", "unipc") else None
@@ -683,6 +690,23 @@ class SamplerState:
             self.plan.ctx.graph_destroy(g)
         self.graphs = {}
         self.keep = self.edit_mask = self.x_plain = None  # (no graph is left that reads them)
+
+    # ---- upload-once tables: a sampler asks "fresh?" in front of chain.upload_lock and loads under it only then, so the
+    # key object of an unchanged table stays the one that was stored
+    def coefs_fresh(self, key):
+        return self._coef_key != key
+
+    def load_coefs(self, key, table):
+        """The first len(table) coefficient rows (PLMS fills S of its S + 1)."""
+        self.coefs[:table.shape[0]].copy_(table)
+        self._coef_key = key
+
+    def scale_fresh(self, key):
+        return self._nscale_key != key
+
+    def load_noise_scale(self, key, scale):
+        self._nscale = scale.to(self.plan.dev)
+        self._nscale_key = key
 
     def ensure_noise(self):
         if self.noise is None:

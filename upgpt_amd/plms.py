@@ -96,18 +96,10 @@ class PLMSSampler(DDIMSampler):
 
     def _fast_plms(self, cond, shape, x_T, timesteps, callback, img_callback, log_every_t, cfg_scale, uc,
                    noise_keys=None):
-        model = self.model
-        unet = model.model.diffusion_model
-        b, C, H, W = shape
-        cfg = uc is not None and cfg_scale != 1.
-        if cfg:
-            cond = self._cat_cond(uc, cond)
-        c_concat, c_cross = model._split_cond(cond)
         S = int(timesteps.shape[0])
-        plan = unet.plan(2 * b if cfg else b, H, W, c_cross.shape[1], S + 1, "sampler")  # rows = model evaluations
+        plan, st, c_concat, c_cross, cfg = self._open_fast("plms", cond, shape, cfg_scale, uc, rows=S + 1)  # rows = model evaluations
         dev = plan.dev
         with torch.cuda.device(dev):
-            st = plan.sampler_state("plms", C, cfg)
             order = np.arange(S)[::-1].copy()
             t_desc = np.asarray(timesteps)[order].astype(np.float32)
             # evaluation k runs at: t_0, then (x~, t_next = t_1) for the Euler corrector, then t_1, t_2, ...
@@ -116,36 +108,24 @@ class PLMSSampler(DDIMSampler):
             f64b = lambda v: np.asarray(v, dtype=np.float64).tobytes()
             rkey = ("plms", t_eval.tobytes())  # (the rows belong to the plan, the coefficients to this state: ddim.py)
             ckey = (f64b(self.ddim_alphas), f64b(self.ddim_alphas_prev), f64b(self.ddim_sigmas))
-            fresh_rows = getattr(plan, "_t_rows_key", None) != rkey
-            fresh_coefs = getattr(st, "_coef_key", None) != ckey
-            fresh = fresh_rows or fresh_coefs
+            fresh_coefs = st.coefs_fresh(ckey)
+            fresh = plan.rows_fresh(rkey) or fresh_coefs
             on_host = chain.on_host(x_T, c_concat, c_cross)
             with chain.upload_lock(fresh or on_host):
                 st.x.copy_(chain.start_latent(x_T, noise_keys, shape, dev, torch.float32))
-                plan.load_sampler_inputs(torch.cat([st.x, st.x]) if cfg else st.x, c_concat, c_cross, unet.in_channels,
-                                         rkey, t_eval)
+                plan.load_sampler_inputs(torch.cat([st.x, st.x]) if cfg else st.x, c_concat, c_cross,
+                                         plan.arch.in_channels, rkey, t_eval)
                 if fresh_coefs:
-                    st.coefs[:S].copy_(ddim_coefficient_table(self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sigmas,
-                                                              self.ddim_sqrt_one_minus_alphas, order))
-                    st._coef_key = ckey
+                    st.load_coefs(ckey, ddim_coefficient_table(self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sigmas,
+                                                               self.ddim_sqrt_one_minus_alphas, order))
                 for _ in range(S + 1 if noise_keys is None else 0):  # the reference draws (and, eta being 0, discards) one noise tensor per update:
                     torch.randn(shape, device=dev)  # plms.py get_x_prev_and_pred_x0 — same generator state afterwards
                 plan.step.zero_()
                 plan.prep.run()
-            intermediates = {"x_inter": [st.x.clone()], "pred_x0": [st.x.clone()]}
             print(f"Running PLMS Sampling with {S} timesteps")
             # one model evaluation per graph launch: S + 1 launches from position -1, the predictor evaluation of the first step
-            logged = chain.logged_at(S, log_every_t)
-            for i in chain.run(st, S + 1, 1, True, logged, False, cfg_scale, first=-1):
-                if i < 0:
-                    continue
-                if callback:
-                    callback(i)
-                if img_callback:
-                    img_callback(st.pred_x0.clone(), i)
-                if logged(i):
-                    intermediates["x_inter"].append(st.x.clone())
-                    intermediates["pred_x0"].append(st.pred_x0.clone())
+            intermediates = chain.run_observed(st, st.x.clone(), S, 1, callback, img_callback, log_every_t, False,
+                                               cfg_scale, first=-1)
             return st.x.clone(), intermediates
 
     @torch.no_grad()
