@@ -642,8 +642,33 @@ int upk_dpmpp_2m_step_f32(upk_ctx* ctx, float* x, const float* eps, const float*
 int upk_unipc_step_f32(upk_ctx* ctx, float* x, const float* eps, const float* coefs, const int32_t* step, float* hist,
                        float* x_corr, float* pred_x0, void* xin, int ld_xin, int batch, int c, int hw, float cfg_scale,
                        int cfg, upk_stream stream);
+/* One step of SDE-DPM-Solver++(2M) (Lu et al. 2022: the stochastic form of the 2M update on the data prediction; eta = 0 is
+ * upk_dpmpp_2m_step_f32's update term by term, eta = 1 the sde-dpmsolver++ midpoint form), fp32 NCHW, n = B*C*H*W elements;
+ * row = coefs + 8 * (*step) for the step s -> t, lambda = log(alpha / sigma), h = lambda_t - lambda_s:
+ *   {sigma_s, 1/alpha_s, (sigma_t/sigma_s) exp(-eta h), -alpha_t expm1(-(1 + eta) h), w, sigma_t sqrt(-expm1(-2 eta h)), 0, 0}
+ *   w = h / (2 h_prev) on a second-order row, 0 on a first-order one; row[5] is the row's noise scale, which only the host
+ *   reads (upgpt_amd/schedule.py dpm_sde_coefficient_table).  The rows describe themselves: there is no first_row.
+ *   e  = eps, or with cfg != 0 e_u + cfg_scale * (e_c - e_u) from eps = [uncond ; cond] (2*batch rows)
+ *   m  = (x - row[0]*e) * row[1]
+ *   d  = row[4] != 0 ? m + row[4] * (m - m_old) : m
+ *   xn = row[2]*x + row[3]*d [+ noise[*step * n + i]]
+ *   x_plain = xn (may be NULL)
+ *   mask != NULL and *step + 1 < n_rows:  xn = mask * keep[(*step + 1) * n + i] + (1 - mask) * xn
+ *   x = xn;  m_old = m;  pred_x0 = m (may be NULL)
+ * noise: [rows, n] fp32 indexed by *step, ALREADY scaled by row[5] * temperature, or NULL (eta = 0).  keep / mask / n_rows /
+ * x_plain: as for upk_ddim_step_edit_f32 — the blend in front of the NEXT evaluation, the last row's result unblended; mask
+ * == NULL ignores keep and n_rows.  m_old: fp32 [n], the data prediction of the step before, owned by the caller; READ ONLY
+ * where row[4] != 0 (it needs no initialisation: a chain's first row is first-order) and always written.  step == NULL:
+ * row 0.  Refreshes the UNet stem input xin from what went to x (with cfg both halves, 2*batch*hw rows); honours
+ * upk_step_autoadvance.  UPK_EINVAL for a missing operand (x, eps, coefs, m_old), a mask without keep rows, a non-positive
+ * extent, ld_xin < c with xin, or a pointer that is not aligned to its element. */
+int upk_dpmpp_2m_sde_step_f32(upk_ctx* ctx, float* x, const float* eps, const float* coefs, const float* noise,
+                              const float* keep, const float* mask, int n_rows, const int32_t* step, float* m_old,
+                              float* pred_x0, float* x_plain, void* xin, int ld_xin, int batch, int c, int hw,
+                              float cfg_scale, int cfg, upk_stream stream);
 /* With done != NULL the sampler step kernels launched afterwards (upk_ddim_step_f32, upk_ddim_step_cfg_f32,
- * upk_ddim_step_edit_f32, upk_plms_step_f32, upk_ddpm_step_f32, upk_dpmpp_2m_step_f32, upk_unipc_step_f32) add 1 to *step THEMSELVES once every workgroup has read it (done: a zero-initialised device
+ * upk_ddim_step_edit_f32, upk_plms_step_f32, upk_ddpm_step_f32, upk_dpmpp_2m_step_f32, upk_unipc_step_f32,
+ * upk_dpmpp_2m_sde_step_f32) add 1 to *step THEMSELVES once every workgroup has read it (done: a zero-initialised device
  * int32 they use as arrival counter and leave at zero) — one launch less per sampler step than upk_advance_step.
  * done == NULL restores the plain behaviour.  Host-side state of the context: set it around the calls. */
 int upk_step_autoadvance(upk_ctx* ctx, int32_t* done);

@@ -26,7 +26,7 @@ SYMBOLS = [
     "upk_groupnorm_num_paths", "upk_groupnorm_path_name", "upk_groupnorm_plan",
     "upk_layernorm_f16", "upk_timestep_embed_f16",
     "upk_nchw_f32_to_nhwc_f16", "upk_nhwc_f16_to_nchw_f32", "upk_f32_to_f16", "upk_ddim_step_f32",
-    "upk_ddim_step_cfg_f32", "upk_ddim_step_edit_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_dpmpp_2m_step_f32", "upk_unipc_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
+    "upk_ddim_step_cfg_f32", "upk_ddim_step_edit_f32", "upk_plms_step_f32", "upk_ddpm_step_f32", "upk_dpmpp_2m_step_f32", "upk_unipc_step_f32", "upk_dpmpp_2m_sde_step_f32", "upk_attention_causal_f16", "upk_attention_qproj_f16", "upk_embed_tokens_f16",
     "upk_attention_fewkeys_f16", "upk_gelu_f16",
     "upk_attention_num_variants", "upk_attention_variant_name", "upk_attention_override", "upk_attention_plan",
     "upk_attention_qproj_plan",
@@ -213,6 +213,8 @@ def load_library(path=None):
             "upk_plms_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),
             "upk_dpmpp_2m_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]),
             "upk_unipc_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),
+            "upk_dpmpp_2m_sde_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32,
+                                                    i32, vp]),
             "upk_ddpm_step_f32": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
             "upk_image_finish_u8": (C.c_int, [vp, vp, i32, i32, i32, i32, i64, i32, i32, i32, i32, vp, i64, i32, i64, i32,
                                               C.POINTER(C.c_float), vp]),
@@ -472,6 +474,14 @@ class Context:
         self._chk(self.lib.upk_unipc_step_f32(self.h, _ptr(x), _ptr(eps), _ptr(coefs), _ptr(step), _ptr(hist),
                                               _ptr(x_corr), _ptr(pred_x0), _ptr(xin), ld_xin, batch, c, hw,
                                               float(cfg_scale), int(cfg), self._s()))
+
+    def dpmpp_2m_sde_step(self, x, eps, coefs, noise, keep, mask, n_rows, step, m_old, pred_x0, x_plain, xin, ld_xin, batch,
+                          c, hw, cfg_scale=1.0, cfg=False):
+        """upk_dpmpp_2m_sde_step_f32: noise [rows, n] is already scaled; m_old is read only where the row's w is non-zero."""
+        self._chk(self.lib.upk_dpmpp_2m_sde_step_f32(self.h, _ptr(x), _ptr(eps), _ptr(coefs), _ptr(noise), _ptr(keep),
+                                                     _ptr(mask), int(n_rows), _ptr(step), _ptr(m_old), _ptr(pred_x0),
+                                                     _ptr(x_plain), _ptr(xin), ld_xin, batch, c, hw, float(cfg_scale),
+                                                     int(cfg), self._s()))
 
     def image_finish(self, src, layout, batch, src_h, src_w, src_bs, top, left, crop_h, crop_w, dst, pitch, dst_x,
                      dst_bs, mode, denorm=None):

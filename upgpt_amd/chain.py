@@ -1,5 +1,5 @@
-"""The captured-chain driver the five samplers share (DDIM with its editing chains, PLMS, DDPM ancestral, DPM-Solver++(2M),
-UniPC):
+"""The captured-chain driver the six samplers share (DDIM with its editing chains, PLMS, DDPM ancestral, DPM-Solver++(2M),
+UniPC, SDE-DPM-Solver++(2M) with its editing chains):
 how a chain's steps are grouped into graph launches, the loop that launches the groups and hands control back to the
 sampler between them, the start latent, and the lock rule in front of the loop.  The four samplers of the
 DDIM family observe a chain the same way, so their host work after a group is here too (run_observed); DDPM's differs
@@ -91,6 +91,7 @@ def upload_lock(take):
       PLMS  fresh or on_host                                 # eta = 0: its discarded draws touch no table
       DPM   fresh or on_host or (x_T is None and not keyed)  # the only draw is x_T
       UniPC as DPM
+      SDE-DPM as DDIM                                        # eta > 0 draws per step; keyed or eta = 0 draws into no table
       DDPM  always                                           # uploads its coefficient and temperature rows every call
 
     fresh: a timestep-row, coefficient or noise-scale table of this call differs from what the device holds."""

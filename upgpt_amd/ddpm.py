@@ -645,8 +645,10 @@ class LatentDiffusion(AncestralSampling, DDPM):
         DPM-Solver++(2M) on its logSNR grid (dpm_solver.py) or "unipc" for UniPC on the same grid (unipc.py; its order /
         variant / corrector arguments pass through **kwargs, and it refuses a masked chain) — ddim_steps is then the step
         count, and `eta`, DDIM's knob (log_images passes its ddim_eta default of 1), does not apply to the deterministic
-        solvers and is dropped."""
-        require(sampler in ("ddim", "dpmpp_2m", "unipc"), lambda: "sampler %r (ddim, dpmpp_2m or unipc)" % (sampler,), ValueError)
+        solvers and is dropped.  "dpmpp_2m_sde" is SDE-DPM-Solver++(2M) (dpm_sde.py), which takes `eta` (0 .. 1) and masked
+        chains, both on its captured path."""
+        require(sampler in ("ddim", "dpmpp_2m", "unipc", "dpmpp_2m_sde"),
+                lambda: "sampler %r (ddim, dpmpp_2m, unipc or dpmpp_2m_sde)" % (sampler,), ValueError)
         if not ddim:
             return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, **kwargs)
         shape = (self.channels, *self.image_size)
@@ -658,6 +660,9 @@ class LatentDiffusion(AncestralSampling, DDPM):
             from .unipc import UniPCSampler
             kwargs.pop("eta", None)
             return UniPCSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
+        if sampler == "dpmpp_2m_sde":
+            from .dpm_sde import DPMSolverSDESampler
+            return DPMSolverSDESampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
         return DDIMSampler(self).sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
 
     def _get_denoise_row_from_list(self, samples, desc="", force_no_decoder_quantization=False):
@@ -718,16 +723,19 @@ class LatentDiffusion(AncestralSampling, DDPM):
                 mask = torch.ones(n, h, w, device=self.device)
                 mask[:, h // 4:3 * h // 4, w // 4:3 * w // 4] = 0.
                 mask = mask[:, None, ...]
+                # (the masked rows are DDIM's, as the reference's, also under sampler="dpmpp_2m" / "unipc"; the solver with
+                # masked chains of its own on the captured path draws them itself)
+                own = {"sampler": "dpmpp_2m_sde"} if kwargs.get("sampler") == "dpmpp_2m_sde" else {}
                 with self.ema_scope("Plotting Inpaint"):
                     samples, _ = self.sample_log(cond=cond, batch_size=n, ddim=use_ddim, eta=ddim_eta,
-                                                 ddim_steps=ddim_steps, x0=z[:n], mask=mask, **keyed(1))
+                                                 ddim_steps=ddim_steps, x0=z[:n], mask=mask, **keyed(1), **own)
                 log["samples_inpainting"] = self.decode_first_stage(samples.to(self.device))
                 log["mask"] = mask
                 # "outpainting" runs with the SAME mask as the inpainting, as the reference does: a second draw of
                 # the same task (its own x_T), not the complementary one
                 with self.ema_scope("Plotting Outpaint"):
                     samples, _ = self.sample_log(cond=cond, batch_size=n, ddim=use_ddim, eta=ddim_eta,
-                                                 ddim_steps=ddim_steps, x0=z[:n], mask=mask, **keyed(2))
+                                                 ddim_steps=ddim_steps, x0=z[:n], mask=mask, **keyed(2), **own)
                 log["samples_outpainting"] = self.decode_first_stage(samples.to(self.device))
         if plot_progressive_rows:
             with self.ema_scope("Plotting Progressives"):

@@ -642,6 +642,11 @@ class SamplerState:
       "unipc": one UniPC model evaluation, upk_unipc_step_f32 (coefficient rows of 12): the corrector of the step that led to
               this point and the predictor of the next.  hist [3, n] is the ring of data predictions and x_corr [n] the last
               corrected latent; the rows say which of them exist, so nothing initialises them either.
+      "dpm_sde": one SDE-DPM-Solver++(2M) step, upk_dpmpp_2m_sde_step_f32 (coefficient rows of 8, entry 5 the host's noise scale);
+              m_old [n] is the data prediction of the step before, read only where a row's w is non-zero.  The noise table
+              is allowed (eta > 0).  None = no mask; "masked" = the keep table, the expanded mask and x_plain of
+              ensure_edit(), as DDIM's masked variant.  A chain that starts at loop position k > 0 presets plan.step to k and
+              loads a table built for it (start = k) into rows k .. S - 1.
     cfg: classifier-free guidance — the plan runs 2*B rows ([unconditional ; conditional], ddim.py:173-178), the latent
     state has B = plan.B // 2 samples and the update combines the two halves of eps."""
 
@@ -660,7 +665,7 @@ class SamplerState:
         self.C = channels
         self.x = plan.alloc(B, channels, H, W, dtype=torch.float32)
         self.pred_x0 = plan.alloc(B, channels, H, W, dtype=torch.float32)
-        self.coefs = plan.alloc(R, {"ddpm": 8, "dpm": 8, "unipc": 12}.get(kind, 4), dtype=torch.float32)
+        self.coefs = plan.alloc(R, {"ddpm": 8, "dpm": 8, "unipc": 12, "dpm_sde": 8}.get(kind, 4), dtype=torch.float32)
         self.noise = None
         self._coef_key = None  # what `coefs` holds (load_coefs)
         self._nscale_key = self._nscale = None  # keyed DDIM's per-row noise scale on the device (load_noise_scale)
@@ -669,6 +674,7 @@ class SamplerState:
         self.hist = plan.alloc(3, B * channels * H * W, dtype=torch.float32) if kind in ("plms", "unipc") else None
         self.x_corr = plan.alloc(B * channels * H * W, dtype=torch.float32) if kind == "unipc" else None
         self.x0_old = plan.alloc(B * channels * H * W, dtype=torch.float32) if kind == "dpm" else None
+        self.m_old = plan.alloc(B * channels * H * W, dtype=torch.float32) if kind == "dpm_sde" else None
         self.set_variant((0, False) if kind == "ddpm" else None)
 
     def set_variant(self, variant):
@@ -676,7 +682,8 @@ class SamplerState:
         if self.kind == "ddpm":
             ok = isinstance(variant, tuple) and len(variant) == 2 and isinstance(variant[0], int) and isinstance(variant[1], bool)
         else:
-            ok = variant is None or (self.kind == "ddim" and variant in ("plain", "masked"))
+            ok = variant is None or (self.kind == "ddim" and variant in ("plain", "masked")) or \
+                (self.kind == "dpm_sde" and variant == "masked")
         require(ok, lambda: "a %r sampler state has no step variant %r" % (self.kind, variant), ValueError)
         self.variant = variant
 
@@ -696,9 +703,10 @@ class SamplerState:
     def coefs_fresh(self, key):
         return self._coef_key != key
 
-    def load_coefs(self, key, table):
-        """The first len(table) coefficient rows (PLMS fills S of its S + 1)."""
-        self.coefs[:table.shape[0]].copy_(table)
+    def load_coefs(self, key, table, row0=0):
+        """The len(table) coefficient rows from row0 on (PLMS fills S of its S + 1; a "dpm_sde" chain from loop position k
+        its rows k .. S - 1)."""
+        self.coefs[row0:row0 + table.shape[0]].copy_(table)
         self._coef_key = key
 
     def scale_fresh(self, key):
@@ -778,7 +786,16 @@ class SamplerState:
             self.x_corr.data_ptr(), self.pred_x0.data_ptr(), p.xin.t.data_ptr(), p.xin.ld, self.B, self.C, p.H * p.W,
             float(scale), int(self.cfg))
 
-    _STEP = {"ddim": _ddim_step, "plms": _plms_step, "ddpm": _ddpm_step, "dpm": _dpm_step, "unipc": _unipc_step}
+    def _dpm_sde_step(self, nz, scale):
+        p = self.plan
+        ptr = (lambda t: t.data_ptr()) if self.variant == "masked" else (lambda t: None)
+        return p.lib.upk_dpmpp_2m_sde_step_f32, (
+            self.x.data_ptr(), p.eps.data_ptr(), self.coefs.data_ptr(), nz, ptr(self.keep), ptr(self.edit_mask), p.rows,
+            p.step.data_ptr(), self.m_old.data_ptr(), self.pred_x0.data_ptr(), ptr(self.x_plain), p.xin.t.data_ptr(),
+            p.xin.ld, self.B, self.C, p.H * p.W, float(scale), int(self.cfg))
+
+    _STEP = {"ddim": _ddim_step, "plms": _plms_step, "ddpm": _ddpm_step, "dpm": _dpm_step, "unipc": _unipc_step,
+             "dpm_sde": _dpm_sde_step}
 
     def _ensure(self, with_noise):
         """The buffers the step of (kind, variant) reads besides the state's own."""
@@ -786,7 +803,7 @@ class SamplerState:
             self.ensure_noise()
         if self.kind == "ddpm" and self.variant[1]:
             self.ensure_mask()
-        if self.kind == "ddim" and self.variant == "masked":
+        if self.kind in ("ddim", "dpm_sde") and self.variant == "masked":
             self.ensure_edit()
 
     def _emit_tail(self, stream, with_noise, scale=1.0):

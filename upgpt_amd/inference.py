@@ -185,7 +185,8 @@ class InferenceModel:
     def generate(self, batch, steps=200, repeat=1, use_ema=True, sampler="ddim", noise_keys=None):
         """log_images with the demo's settings -> {'reconstruction'?, 'samples'} as float numpy [b, h, w, 3] in [0, 1]
         (:160-170; `repeat` is unused there as well).  sampler: "ddim" (the reference's), "dpmpp_2m" for
-        DPM-Solver++(2M) or "unipc" for UniPC, each with `steps` steps (LatentDiffusion.sample_log).  noise_keys (upgpt_amd.rng.NoiseKeys, one key
+        DPM-Solver++(2M), "unipc" for UniPC or "dpmpp_2m_sde" for SDE-DPM-Solver++(2M) (stochastic: log_images' eta of 1), each
+        with `steps` steps (LatentDiffusion.sample_log).  noise_keys (upgpt_amd.rng.NoiseKeys, one key
         per sample): handed to log_images, which then draws keyed noise instead of the torch generator's."""
         extra = {} if sampler == "ddim" else {"sampler": sampler}
         if noise_keys is not None:

@@ -1,11 +1,14 @@
-"""MultistepSolverSampler — what DPMSolverSampler and UniPCSampler share: deterministic multistep solvers on the data
-prediction of an eps-parameterised model, on a grid uniform in lambda = log(alpha / sigma), with DDIMSampler's surface.
+"""MultistepSolverSampler — what DPMSolverSampler, UniPCSampler and DPMSolverSDESampler share: multistep solvers on the data
+prediction of an eps-parameterised model (the first two deterministic, the third with DDIM's eta: dpm_sde.py), on a grid
+uniform in lambda = log(alpha / sigma), with DDIMSampler's surface.
 
 Here, once: the "logsnr" grid, the checks and the schedule cache of sample(), the dispatch between the two paths, the
 fast path (the captured graphs of engine.SamplerState kind KIND, opened by DDIMSampler._open_fast and run by
 chain.run_observed) and the general path (one apply_model and one eager step-kernel launch per step from Python).
 A solver supplies NAME and KIND, _table (its coefficient rows for a chain), _history and _step (its eager buffers and
-kernel call), and overrides _check_mask when it runs no masked chains.
+kernel call), and overrides _check_mask when it runs no masked chains and _check_eta when it takes an eta other than 0;
+a solver that draws step noise hands _general its `draw` (dpm_sde.py, which also has a fast path of its own: its chains
+carry a noise table and a mask).
 """
 import numpy as np
 import torch
@@ -35,6 +38,11 @@ class MultistepSolverSampler(DDIMSampler):
         """One eager launch of the step kernel on the table row `row`."""
         raise NotImplementedError
 
+    def _check_eta(self, eta):
+        """Raises for an eta the solver does not run."""
+        if eta != 0:
+            raise ValueError("%s is deterministic: eta must be 0 (got %r)" % (self.NAME, eta))
+
     def _check_mask(self, mask, x0):
         """Raises where the solver runs no masked chain; the general path blends q_sample(x0, t) in front of every
         evaluation otherwise."""
@@ -51,9 +59,8 @@ class MultistepSolverSampler(DDIMSampler):
     def _make_grid(self, ddim_num_steps, ddim_discretize, ddim_eta, verbose):
         """DDIMSampler's tables on the chosen grid (alphas_prev[0] = alphas_cumprod[0] is the chain's last target on every
         grid); drops the general path's device copies of the coefficient rows."""
-        if ddim_eta != 0:
-            raise ValueError("%s is deterministic: eta must be 0 (got %r)" % (self.NAME, ddim_eta))
-        super().make_schedule(ddim_num_steps, ddim_discretize, ddim_eta, verbose)
+        self._check_eta(ddim_eta)
+        super().make_schedule(ddim_num_steps, ddim_discretize, 0., verbose)  # (DDIM's sigmas are not the solvers')
         self._dev_tables = {}  # start -> (device, rows, row indices)
 
     def _sample(self, S, batch_size, shape, discretize, solver, normals_sequence, eta, verbose, noise_keys, cond,
@@ -61,13 +68,12 @@ class MultistepSolverSampler(DDIMSampler):
         """The body of sample(): `solver` = the solver's own make_schedule arguments in its signature's order (they key
         the schedule cache), `run` = what goes on to _sampling."""
         rng.check_keys(noise_keys, batch_size, normals_sequence)
-        if eta != 0:
-            raise ValueError("%s is deterministic: eta must be 0 (got %r)" % (self.NAME, eta))
+        self._check_eta(eta)
         require(getattr(self.model, "parameterization", "eps") == "eps",
                 "%s here takes an eps-parameterised model" % self.NAME, NotImplementedError)
         self._check_mask(mask, x0)
-        self._ensure_schedule((int(S), str(discretize)) + tuple(solver.values()),
-                              lambda: self.make_schedule(S, discretize, 0., verbose, **solver), verbose)
+        self._ensure_schedule((int(S), str(discretize), float(eta)) + tuple(solver.values()),
+                              lambda: self.make_schedule(S, discretize, float(eta), verbose, **solver), verbose)
         C, H, W = shape
         size = (batch_size, C, H, W)
         print(f"Data shape for {self.NAME} sampling is {size}")
@@ -105,10 +111,12 @@ class MultistepSolverSampler(DDIMSampler):
         return held[1], held[2], k - start
 
     def _general(self, img, cond, timesteps, callback, img_callback, log_every_t, mask, x0, score_corrector,
-                 corrector_kwargs, cfg_scale, uc, noise_keys):
+                 corrector_kwargs, cfg_scale, uc, noise_keys, draw=None):
         """One apply_model and one eager step per step.  A chain of T steps starts at loop position k = S - T: the first
         row it reads is first-order (the history is not this chain's).  mask / x0: the reference's blend with
-        q_sample(x0, t) in front of every evaluation (ddim.py:144-147, as plms_sampling does it)."""
+        q_sample(x0, t) in front of every evaluation (ddim.py:144-147, as plms_sampling does it).  draw(i) (a solver with step
+        noise): what its _step takes as last argument for loop position k + i — the step's noise, drawn after that
+        position's q_sample draw."""
         device = img.device
         shape = tuple(img.shape)
         b, C, hw = shape[0], shape[1], shape[2] * shape[3]
@@ -133,9 +141,10 @@ class MultistepSolverSampler(DDIMSampler):
             in_kernel = guided and score_corrector is None
             e = self._guided_eps(x, ts, cond, cfg_scale, uc, score_corrector, corrector_kwargs, combine=not in_kernel)
             pred_x0 = torch.empty_like(x)
+            nz = () if draw is None else (draw(i),)
             with torch.cuda.device(device):
                 self._step(ctx, x, e.float().contiguous(), coefs, rows[r0 + i:r0 + i + 1], history, pred_x0, b, C, hw, r0,
-                           cfg_scale if in_kernel else 1., in_kernel)
+                           cfg_scale if in_kernel else 1., in_kernel, *nz)
             if callback:
                 callback(i)
             if img_callback:

@@ -6,7 +6,7 @@ DDIM selection and sigmas per util.py:46-74.  The per-step scalars that the refe
 re-materialises with torch.full every step (ddim.py:189-192) are folded here into ONE
 device table of 4 fp32 coefficients per step for upk_ddim_step_f32 (8 per step for the DDPM
 step, upk_ddpm_step_f32, and for the DPM-Solver++(2M)
-step, upk_dpmpp_2m_step_f32; 12 for the UniPC step, upk_unipc_step_f32).
+step, upk_dpmpp_2m_step_f32, and its SDE form, upk_dpmpp_2m_sde_step_f32; 12 for the UniPC step, upk_unipc_step_f32).
 """
 import numpy as np
 import torch
@@ -107,6 +107,45 @@ def dpm_coefficient_table(alphas, alphas_prev, order=2, lower_order_final=None):
     rows = np.zeros((S, 8))
     rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3], rows[:, 4] = sg_t, 1.0 / al_t, sg_p / sg_t, -al_p * np.expm1(-h), w
     return torch.from_numpy(rows.astype(np.float32)).contiguous()
+
+
+def dpm_sde_coefficient_table(alphas, alphas_prev, eta=1.0, order=2, lower_order_final=None, start=0):
+    """[S - start, 8] fp32 rows of upk_dpmpp_2m_sde_step_f32 in LOOP order from the DDIM tables `alphas` / `alphas_prev`
+    (ascending index).  Points k = 0 .. S as in unipc_coefficient_table; the chain starts at point `start` with no history.
+    Row i - start is the step s -> t from point i to point i + 1, h = lambda_t - lambda_s > 0:
+        {sigma_s, 1 / alpha_s, (sigma_t / sigma_s) exp(-eta h), -alpha_t expm1(-(1 + eta) h), w, sigma_t sqrt(-expm1(-2 eta h)), 0, 0}
+    w = h_i / (2 h_{i-1}) on a second-order row, 0 on a first-order one: the order of row i is min(order, i + 1 - start), and
+    the last row is first-order with lower_order_final (None: S < 15, DPMSolverSampler's rule).  Entry 5 is the row's noise
+    scale, read by the host only (0 exactly when eta = 0).  eta = 0: dpm_coefficient_table's rows.  Computed in fp64 and
+    rounded once."""
+    if order not in (1, 2):
+        raise ValueError("dpm_sde_coefficient_table: order %r (1 or 2)" % (order,))
+    eta = float(eta)
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError("dpm_sde_coefficient_table: eta %r outside [0, 1]" % (eta,))
+    f64 = lambda v: np.asarray(torch.as_tensor(v).detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float64)
+    a_t, a_p = f64(alphas)[::-1], f64(alphas_prev)[::-1]
+    S, start = int(a_t.shape[0]), int(start)
+    if not 0 <= start < S:
+        raise ValueError("dpm_sde_coefficient_table: start %d outside the %d-step chain" % (start, S))
+    if lower_order_final is None:
+        lower_order_final = S < 15
+    a = np.concatenate([a_t, a_p[-1:]])  # the S + 1 points
+    al, sg = np.sqrt(a), np.sqrt(1.0 - a)
+    h = np.diff(np.log(al / sg))
+    if not (h > 0).all():
+        raise ValueError("dpm_sde_coefficient_table: the logSNR must rise along the chain")
+    w = np.zeros(S)
+    if order == 2:
+        w[start + 1:] = h[start + 1:] / (2.0 * h[start:-1])
+        if lower_order_final:
+            w[-1] = 0.0
+    rows = np.zeros((S, 8))
+    rows[:, 0], rows[:, 1], rows[:, 4] = sg[:-1], 1.0 / al[:-1], w
+    rows[:, 2] = sg[1:] / sg[:-1] * np.exp(-eta * h)
+    rows[:, 3] = -al[1:] * np.expm1(-(1.0 + eta) * h)
+    rows[:, 5] = sg[1:] * np.sqrt(-np.expm1(-2.0 * eta * h))
+    return torch.from_numpy(rows[start:].astype(np.float32)).contiguous()
 
 
 def _unipc_rho(r, h, variant):
